@@ -17,7 +17,13 @@ its own stream while step k+1's fill runs, with two workspace slots and two outp
 Every step's fill and traceback still lies inside the timed region (it ends with sa_wait + a
 device synchronize); "serial_ms_per_step" reports the same step without overlap.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md §2.5 for the fields).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the result line
+(metric, value, ms_per_step, dtype, the last step's HIP event times).  `--full` adds every other
+leg after the timed region, as one run: the non-pipelined and host-API steps, the oracle parity of
+the batch, the roofline, BASELINE.json's other configs, the C++ drop-in legs and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) as .npy files.
 """
 from __future__ import annotations
 
@@ -80,7 +86,17 @@ def parse():
                     help="headline parity: full op streams checked against the full-matrix oracle "
                          "(every pair's end cell is always checked)")
     ap.add_argument("--latency-reps", type=int, default=200, help="drop-in single-call latency leg (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: serial and host-API steps, oracle parity, "
+                         "roofline, --configs, the C++ drop-in legs and the CPU baselines (the options above that "
+                         "size those legs only matter with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the results and a seeded sample of the op streams of the last timed step to "
+                         "DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port() -> int:
@@ -403,6 +419,59 @@ def gather_parity(par: dict, world: int):
     return out
 
 
+DUMP_SEED = 20240229            # --dump-outputs: which pairs' op streams are sampled
+DUMP_OPS_PAIRS = 512            # at most this many sampled pairs
+DUMP_OPS_BYTES = 48 << 20       # and at most this many bytes of op-stream sample (64 MB in all with the results)
+DUMP_FIELDS = ("score", "end_i", "end_j", "start_i", "start_j", "nops", "flags")
+
+
+def dump_outputs(dirname, sa, d_res, d_ops, o1, o2, rank, world):
+    """--dump-outputs: what the last timed step left in the caller's device buffers, as .npy files
+    (names carry _rank<r> when there is more than one rank):
+
+      results.npy          float64 (P, 7): every pair's score, end_i, end_j, start_i, start_j, nops, flags
+      ops_sample_pairs.npy float64 (K,): the pairs whose op streams are sampled -- a fixed choice
+                           (DUMP_SEED) of K pairs, all of them when the batch is small
+      ops_sample.npy       float32 (K, W): row k = the op stream of pair ops_sample_pairs[k] (its nops
+                           op bytes 'M' / 'S' / 'U' / 'L' as numbers), zero after its end
+
+    The inputs are seeded, so two builds run with the same arguments write comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    res = np.frombuffer(d_res.cpu().numpy().tobytes(), dtype=sa.RESULT_DTYPE)
+    ops = d_ops.cpu().numpy()
+    P = len(res)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirname, f"results{sfx}.npy"), np.stack([res[f].astype(np.float64) for f in DUMP_FIELDS], axis=1))
+    slot = (o1[1:] - o1[:-1]).astype(np.int64) + (o2[1:] - o2[:-1]).astype(np.int64) + 1   # op bytes a pair may take
+    W = int(min(slot.max(), DUMP_OPS_BYTES // 4))
+    K = int(min(P, DUMP_OPS_PAIRS, DUMP_OPS_BYTES // (4 * W)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(P, K, replace=False))
+    sample = np.zeros((K, W), dtype=np.float32)
+    for k, p in enumerate(idx):
+        off = int(o1[p] + o2[p]) + int(p)
+        n = min(int(res["nops"][p]), int(slot[p]), W)
+        sample[k, :n] = ops[off:off + n]
+    np.save(os.path.join(dirname, f"ops_sample_pairs{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, f"ops_sample{sfx}.npy"), sample)
+
+
+def write_rank_out(dirname, rank, world, own, elapsed, seed_base, P, par, res, eng):
+    """--rank-out: this rank's own time, shard and (with --full) parity, as rank<r>.json."""
+    os.makedirs(dirname, exist_ok=True)
+    with open(os.path.join(dirname, f"rank{rank}.json"), "w") as f:
+        json.dump({"rank": rank, "world": world, "own_s": own, "max_s": elapsed, "seed_base": seed_base, "pairs": P,
+                   "parity": par, "flags": int(np.count_nonzero(res["flags"])) if res is not None else None,
+                   "plan": list(eng.last_plan())}, f)
+
+
+def emit(line: dict, out: str):
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(txt + "\n")
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -459,6 +528,45 @@ def main():
     fill_ms, tb_ms, launches = eng.last_timings()   # HIP events of the last step (fill stream / traceback stream)
     fill_kernel_ms, _ = eng.last_kernel_timings()    # the fill kernel alone (without the end-cell replay)
     last = (args.steps - 1) % NSET
+    fill_ms = max_over_ranks(fill_ms, world)
+    fill_kernel_ms = max_over_ranks(fill_kernel_ms, world)
+    cells_rank = float(P) * Lq * Lq
+    cells_job = float(args.total_pairs) * Lq * Lq if args.total_pairs > 0 else world * cells_rank
+    value = cells_job * args.steps / elapsed / 1e9
+    ms_per_step = elapsed / args.steps * 1e3
+    kernel, plan_R, plan_W, records = eng.last_plan_ex()
+    t16 = kernel in (sa.SA_KERNEL_T16, sa.SA_KERNEL_T16_ENDCELL)
+    endcell = kernel == sa.SA_KERNEL_T16_ENDCELL
+    so = records == sa.SA_RECORDS_SCORE_ONLY
+    # two pairs per wave (sa_fill_so2.hip) on the score-only SW plans at R = 16 / 32 unless SEQALIB_SO2=0
+    so2 = so and plan_R in (16, 32) and os.environ.get("SEQALIB_SO2", "1") != "0"
+    # the f16 cell (sa_fill_so2.hip FK) as the engine picks it (sa_api.hip so2_f16_scoring): SW at
+    # an f16-exact match / mismatch unless SEQALIB_SO2_F16=0 (random DNA never turns it off)
+    f16 = so2 and os.environ.get("SEQALIB_SO2_F16", "1") != "0" and all(f16_hi_exact(x) for x in (SCORING[1], SCORING[2]))
+    line = {
+        "metric": METRIC, "value": round(value, 2), "unit": "GCUPS", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
+        "scaling": "strong" if args.total_pairs > 0 else "weak", "vs_baseline": None, "dtype": ("f16 (integer-exact below 2048)" if f16 else "int16") if t16 else "int32",
+        "data": "synthetic DNA, std::mt19937_64 'ACGT'[g()&3], seeds base+2p+1/base+2p+2, resident in HBM",
+        "config": {"workload": workload, "pairs_per_gpu": P, "total_pairs": args.total_pairs or world * P,
+                   "m": Lq, "n": Lq, "algo": "SmithWatermanSA",
+                   "scoring": list(SCORING), "match": "equal<char>", "parallelism": f"pair-shard x{world}"},
+        "fill_ms": round(fill_ms, 2), "fill_kernel_ms": round(fill_kernel_ms, 2),
+        "endcell_ms": round(fill_ms - fill_kernel_ms, 2), "traceback_ms": round(tb_ms, 2),
+        "timings_basis": "HIP events of the last timed step: fill_ms = fill stream (fill kernel + end-cell "
+                         "replay), traceback_ms = traceback stream after the fill stream",
+        "records": "score-only fill + block-recompute traceback" if so else ("tagged" if t16 else "flags"),
+        "pipelined": pipelined, "full": args.full,
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sa, d_res[last], d_ops[last], o1, o2, rank, world)
+    if not args.full:
+        # a plain run ends here: nothing below is needed for the headline figure
+        if args.rank_out:
+            write_rank_out(args.rank_out, rank, world, own, elapsed, seed_base, P, None, None, eng)
+        if rank == 0:
+            emit(line, args.out)
+        return
     serial_ms = None
     if pipelined and args.serial_steps > 0:
         # the same steps without overlap, for reference (outside the timed region above)
@@ -469,9 +577,6 @@ def main():
             step(last + 1 + NSET * k)   # another output set: keeps the checked one intact
         torch.cuda.synchronize()
         serial_ms = max_over_ranks(time.perf_counter() - ts, world) / args.serial_steps * 1e3
-    kernel, plan_R, plan_W = eng.last_plan()
-    fill_ms = max_over_ranks(fill_ms, world)
-    fill_kernel_ms = max_over_ranks(fill_kernel_ms, world)
     # end to end through the host API (what the C++ drop-in does): sequences H2D, fill, end cell,
     # traceback, results + op streams D2H; outside the timed region
     e2e_ms, e2e_each = None, None
@@ -486,12 +591,6 @@ def main():
             out = eng.align_packed(sa.SA_SW, sc_, s1, o1, s2, o2, out=out)   # caller keeps its buffers
             e2e_each.append(round((time.perf_counter() - tc) * 1e3, 2))
         e2e_ms = max_over_ranks(time.perf_counter() - te, world) / args.e2e_steps * 1e3
-
-    cells_rank = float(P) * Lq * Lq
-    cells_job = float(args.total_pairs) * Lq * Lq if args.total_pairs > 0 else world * cells_rank
-    value = cells_job * args.steps / elapsed / 1e9
-    ms_per_step = elapsed / args.steps * 1e3
-    kernel, plan_R, plan_W, records = eng.last_plan_ex()
 
     # parity of this rank's batch, outside the timed region: every pair's (MaxScore, MaxRow, MaxCol)
     # against the linear-space oracle, every alignment re-scored to the reported maximum, and
@@ -510,22 +609,11 @@ def main():
         configs = measure(sa, torch, eng, dev, set(args.configs.split(",")), cores)
 
     if args.rank_out:
-        os.makedirs(args.rank_out, exist_ok=True)
-        with open(os.path.join(args.rank_out, f"rank{rank}.json"), "w") as f:
-            json.dump({"rank": rank, "world": world, "own_s": own, "max_s": elapsed, "seed_base": seed_base, "pairs": P,
-                       "parity": par, "flags": int(np.count_nonzero(res["flags"])), "plan": list(eng.last_plan())}, f)
+        write_rank_out(args.rank_out, rank, world, own, elapsed, seed_base, P, par, res, eng)
     if rank != 0:
         return
     per_launch_cells = cells_rank  # one fill launch covers the whole batch when it fits HBM
     fill_s = fill_kernel_ms / 1e3 / max(launches, 1)   # one fill kernel launch (HIP events on its stream)
-    t16 = kernel in (sa.SA_KERNEL_T16, sa.SA_KERNEL_T16_ENDCELL)
-    endcell = kernel == sa.SA_KERNEL_T16_ENDCELL
-    so = records == sa.SA_RECORDS_SCORE_ONLY
-    # two pairs per wave (sa_fill_so2.hip) on the score-only SW plans at R = 16 / 32 unless SEQALIB_SO2=0
-    so2 = so and plan_R in (16, 32) and os.environ.get("SEQALIB_SO2", "1") != "0"
-    # the f16 cell (sa_fill_so2.hip FK) as the engine picks it (sa_api.hip so2_f16_scoring): SW at
-    # an f16-exact match / mismatch unless SEQALIB_SO2_F16=0 (random DNA never turns it off)
-    f16 = so2 and os.environ.get("SEQALIB_SO2_F16", "1") != "0" and all(f16_hi_exact(x) for x in (SCORING[1], SCORING[2]))
     label = f"sw_{'so2f' if f16 else 'so2' if so2 else 'so' if so else 't16c' if endcell else 't16' if t16 else 'int32'}_r{plan_R}"
     model = issue_model(label)
     fill_gcups = per_launch_cells / fill_s / 1e9
@@ -578,20 +666,8 @@ def main():
                  "bytes_per_cell": round(bytes_per_cell, 4), "hbm_achieved_GBps": round(hbm_gbps, 1),
                  "fill_streams_bytes_per_launch": streams,
                  "hbm_peak_GBps": HBM_PEAK_GBPS, "hbm_frac": round(hbm_gbps / HBM_PEAK_GBPS, 4)})
-    line = {
-        "metric": METRIC, "value": round(value, 2), "unit": "GCUPS", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
-        "scaling": "strong" if args.total_pairs > 0 else "weak", "vs_baseline": None, "dtype": ("f16 (integer-exact below 2048)" if f16 else "int16") if t16 else "int32",
-        "data": "synthetic DNA, std::mt19937_64 'ACGT'[g()&3], seeds base+2p+1/base+2p+2, resident in HBM",
-        "config": {"workload": workload, "pairs_per_gpu": P, "total_pairs": args.total_pairs or world * P,
-                   "m": Lq, "n": Lq, "algo": "SmithWatermanSA",
-                   "scoring": list(SCORING), "match": "equal<char>", "parallelism": f"pair-shard x{world}"},
+    line.update({
         "roofline": roof,
-        "fill_ms": round(fill_ms, 2), "fill_kernel_ms": round(fill_kernel_ms, 2),
-        "endcell_ms": round(fill_ms - fill_kernel_ms, 2), "traceback_ms": round(tb_ms, 2),
-        "timings_basis": "HIP events of the last timed step: fill_ms = fill stream (fill kernel + end-cell "
-                         "replay), traceback_ms = traceback stream after the fill stream",
-        "records": "score-only fill + block-recompute traceback" if so else ("tagged" if t16 else "flags"),
         "e2e_ms_per_step": round(e2e_ms, 2) if e2e_ms else None,
         "e2e_ms_each": e2e_each if e2e_ms else None,
         "e2e_gcups": round(cells_job / (e2e_ms / 1e3) / 1e9, 1) if e2e_ms else None,
@@ -600,7 +676,7 @@ def main():
                      "A/C/G/T pieces packed to 2 bits on the host and unpacked on the device (host pass over "
                      "piece k+1 beside the H2D of piece k), fill, end cell, traceback, download of results and "
                      "2-bit op streams, expanded into the caller's (reused) buffers as pieces land",
-        "pipelined": pipelined, "serial_ms_per_step": round(serial_ms, 2) if serial_ms else None,
+        "serial_ms_per_step": round(serial_ms, 2) if serial_ms else None,
         "parity": "; ".join(
             (f"rank {r}: " if world > 1 else "")
             + (f"{q['end_cells']} pairs' (MaxScore, MaxRow, MaxCol) bit-exact vs oracle; {q['rescored']} "
@@ -610,7 +686,7 @@ def main():
         "parity_ranks": [{"rank": r, "exact": q["exact"], "end_cells": q["end_cells"], "op_streams": q["op_streams"]}
                          for r, q in enumerate(par_ranks)] if world > 1 else None,
         "configs": configs,
-    }
+    })
     if world == 1:
         eng.L.sa_trim(eng.h)   # free this process's workspace for the children's
         line["dropin_e2e"] = dropin_e2e(args)
@@ -620,11 +696,7 @@ def main():
         line["cpu_baseline_1thread"] = cpu_baseline(args, s1, o1, s2, o2, threads=1, pairs=args.cpu_pairs_1t)
     else:
         line["cpu_baseline"] = None
-    txt = json.dumps(line)
-    print(txt, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(txt + "\n")
+    emit(line, args.out)
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@ def test_two_hip_ranks_gloo(tmp_path, length):
     env = dict(os.environ, SEQALIB_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--pairs", "40", "--len",
-           str(length), "--steps", str(steps), "--warmup", "1", "--no-cpu", "--e2e-steps", "0", "--serial-steps", "0",
+           str(length), "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu", "--e2e-steps", "0", "--serial-steps", "0",
            "--dropin-pairs", "0", "--rank-out", str(tmp_path), "--out", str(tmp_path / "line.json")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -51,13 +51,14 @@ def test_two_hip_ranks_gloo(tmp_path, length):
 
 @pytest.mark.timeout(900)
 def test_bench_gpus2_spawns_two_ranks(tmp_path):
-    """`python3 bench.py --gpus 2 --steps 2 --warmup 1` exactly as the driver starts it for N = 2 --
+    """`python3 bench.py --gpus 2 --steps 2 --warmup 1 --full` as the driver starts it for N = 2 --
     no launcher, no WORLD_SIZE -- must run two ranks (bench.py spawns them), each aligning its own
     10,000-pair shard of the 4096 x 4096 headline workload, and report n_gpus = 2, the max-over-ranks
-    time and exact parity on both shards.  Both ranks share GPU 0 here (SEQALIB_BENCH_DEVICE=0)."""
+    time and (the --full leg) exact parity on both shards.  Both ranks share GPU 0 here
+    (SEQALIB_BENCH_DEVICE=0)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SEQALIB_BENCH_DEVICE="0")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--rank-out", str(tmp_path), "--out", str(tmp_path / "line.json")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])

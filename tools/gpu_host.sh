@@ -12,5 +12,6 @@ for g in 1 2; do
   SEQALIB_HOST_CHUNKS=$g SEQALIB_HOST_TIMING=1 timeout -k 10 200 python tools/host_api_timing.py > gpurun_out/hat_$g.log 2>&1 || { tail -5 gpurun_out/hat_$g.log; exit 1; }
   grep -v amdgpu.ids gpurun_out/hat_$g.log
 done
-timeout -k 10 300 python bench.py --no-cpu --steps 3 --warmup 1 --serial-steps 2 --e2e-steps 3 --dropin-pairs 10000 --dropin-reps 3 > gpurun_out/b.log 2>&1 || { tail -5 gpurun_out/b.log; exit 1; }
-tail -1 gpurun_out/b.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print({k: d[k] for k in ('ms_per_step','e2e_ms_per_step','serial_ms_per_step')}, d['dropin_e2e']['ms_each'])"
+BLOG=$(mktemp)
+timeout -k 10 300 python bench.py --full --no-cpu --steps 3 --warmup 1 --serial-steps 2 --e2e-steps 3 --dropin-pairs 10000 --dropin-reps 3 > "$BLOG" 2>&1 || { tail -5 "$BLOG"; exit 1; }
+tail -1 "$BLOG" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print({k: d[k] for k in ('ms_per_step','e2e_ms_per_step','serial_ms_per_step')}, d['dropin_e2e']['ms_each'])"

@@ -9,7 +9,8 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-r01}
-BENCH_ARGS=${BENCH_ARGS:-}
+# --full: the CPU baseline of step 1 and the roofline that tools/summarize_profile.py reads
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 echo "[profile] bench $(date +%T)"
 timeout -k 10 900 python bench.py $BENCH_ARGS --out gpurun_out/bench_full.json > gpurun_out/bench_full.log 2>&1 || { echo bench failed; tail -20 gpurun_out/bench_full.log; exit 1; }
 cat gpurun_out/bench_full.json
