@@ -667,17 +667,22 @@ int validate_scoring(sa_ctx* c, int algo, const sa_scoring* s) {
 // T16 by scoring and shape (the batch alphabet is checked on the device, decide_t16).
 // The f16 cell of the two-pairs-per-wave SW fill (sa_fill_so2.hip FK): the substitutions the T16
 // fill runs with (match, tm.mismatch) must be f16 values whose low byte is 0 (+-1..8, 10, 12, 14,
-// 16, 20, ...), so that the perm's table byte is their high byte.  $SEQALIB_SO2_F16=0: the 16-bit
-// integer cell (A/B, tests).
+// 16, 20, ...), so that the perm's table byte is their high byte.  Returns FillParams::so2_f16: 2,
+// the 4-op cell on values scaled by 2^-11 (a power of two: the same bytes qualify); $SEQALIB_SO2_F16=5
+// gives 1, the 5-op f16 cell, and =0 gives 0, the 16-bit integer cell (A/B, tests).
 bool f16_hi_exact(int s) {
     if (s < -2048 || s > 2048) return false;
     const _Float16 h = (_Float16)(float)s;
     return (int)(float)h == s && (__builtin_bit_cast(uint16_t, h) & 0xffu) == 0;
 }
-bool so2_f16_scoring(const sa_ctx* c, int algo, const sa_scoring* sc, const T16Mode& tm) {
-    if (algo != SA_SW || !tm.ok || c->f16_off) return false;
-    if (const char* e = getenv("SEQALIB_SO2_F16")) if (e[0] == '0') return false;
-    return f16_hi_exact(sc->match) && f16_hi_exact(tm.mismatch) && f16_hi_exact(-128);
+uint32_t so2_f16_scoring(const sa_ctx* c, int algo, const sa_scoring* sc, const T16Mode& tm) {
+    if (algo != SA_SW || !tm.ok || c->f16_off) return 0;
+    uint32_t cell = 2;
+    if (const char* e = getenv("SEQALIB_SO2_F16")) {
+        if (e[0] == '0') return 0;
+        if (e[0] == '5') cell = 1;
+    }
+    return f16_hi_exact(sc->match) && f16_hi_exact(tm.mismatch) && f16_hi_exact(-128) ? cell : 0;
 }
 
 T16Mode t16_candidate(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs) {
@@ -851,7 +856,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
         const Variant vt = make_variant(algo, max_m, max_n, npairs, true, true);
         const bool bu_hand = vt.so && !is_affine(algo) && (vt.pl.g.bands > 1 || vt.segs > 1);
         // (the f16 cell may flag any pair: its int32 re-run stays)
-        const bool f16 = vt.so2 && so2_f16_scoring(c, algo, sc, tm);
+        const bool f16 = vt.so2 && so2_f16_scoring(c, algo, sc, tm) != 0;
         if (ha->sel == 0) only = 2;
         else if (tm.retry_above == INT_MAX && !bu_hand && !f16) only = 1;
         else sel = prof + 5;
@@ -1074,8 +1079,8 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                 const uint32_t range = std::max((nch + sg - 1) / sg, 3u) * kChunk + kWave;
                 const uint32_t cap = (range + 15) & ~15u;
                 fp.so2_stage = (2 * cap <= 8192 && !no_stage) ? cap : 0;
-                if (v.t16 && so2_f16_scoring(c, algo, sc, tm)) {
-                    fp.so2_f16 = 1;
+                if (const uint32_t cell = v.t16 ? so2_f16_scoring(c, algo, sc, tm) : 0u) {
+                    fp.so2_f16 = cell;
                     fp.retry_above = std::min(fp.retry_above, kSo2F16RetryAbove);
                 }
             }

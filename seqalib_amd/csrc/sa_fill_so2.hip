@@ -48,6 +48,23 @@
 // Rows past a pair's m take s = 0 (the selector's constant byte), columns past its n s = -128:
 // s <= 0 keeps those cells at most the matrix maximum, all the bounds above need.
 //
+// X4 (FK == 2, the SW default wherever the f16 cell qualifies; SEQALIB_SO2_F16=5 keeps FK == 1): the
+// cell on H / 2048, 4 ops per 2 cells (tools/microbench_pk6.hip PK4F).  Scaled by 2^-11 the f16 add's
+// `clamp` ([0, 1]) is the zero floor, so F = max(H + Gap, 0) is one op, and with F kept per row
+// beside H (Fr[r]: 3 R registers of state, R = 32 at 3 waves per SIMD and 168 VGPRs) the max over
+// the up and left candidates needs no add of its own:
+//   p  = v_perm_b32(colB, colA, sel_r)   s / 2048 as an f16 whose low byte is 0 (a power-of-two scale
+//                                        keeps the mantissa: the same scorings qualify)
+//   dn = v_pk_add_f16(hp, p)             Hd + s
+//   hp = v_pk_maximum3_f16(dr, Fu, Fl)   F >= 0 floors it
+//   F  = v_pk_add_f16(hp, Gap / 2048) clamp
+// A lane's upper F is clamp(up + Gap) of the H it takes from the lane above (one op per step; lane
+// 0: the band row), the borders' F is 0, the segment hand-off carries H and the next unit rebuilds
+// F.  k 2^-11 is exact for k < 2048, so the flag and the int32 re-run are FK's; F's upper clamp
+// acts on H + Gap > 2048 only and leaves 2048.  Words for other kernels leave through
+// ONE packed multiply by 2^-13 (k 2^-24 has the bit pattern k: f16 denormals are on) and band rows
+// come back through one by 2^13: no sub-dword (SDWA / op_sel) write anywhere in this cell.
+//
 // ALG = SA_NW (round 6): the same cell without the clamp (SANeedlemanWunsch.h:69-86; registers hold
 // H - delta, the T16 window of t16_mode), the borders i Gap - delta / j Gap - delta in the left
 // column, the corner and band 0's top row, no chunk maxima.  H[m][n] of each pair is taken at the
@@ -90,18 +107,24 @@ __device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
     asm("v_pk_max_i16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
-// both halves: f16 integer -> u16 integer, and back
+// both halves: f16 integer -> u16 integer, and back.  (A dst_sel write followed at once by a VALU
+// read of the register -- the second conversion's UNUSED_PRESERVE read, the statement's first
+// consumer -- needs a wait state the compiler does not put inside or behind an asm string.)
 __device__ __forceinline__ uint32_t f16x2_to_u16x2(uint32_t x) {
     uint32_t d;
     asm("v_cvt_u16_f16_sdwa %0, %1 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_0\n\t"
-        "v_cvt_u16_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1"
+        "s_nop 0\n\t"
+        "v_cvt_u16_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
+        "s_nop 0"
         : "=&v"(d) : "v"(x));
     return d;
 }
 __device__ __forceinline__ uint32_t u16x2_to_f16x2(uint32_t x) {
     uint32_t d;
     asm("v_cvt_f16_u16_sdwa %0, %1 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_0\n\t"
-        "v_cvt_f16_u16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1"
+        "s_nop 0\n\t"
+        "v_cvt_f16_u16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
+        "s_nop 0"
         : "=&v"(d) : "v"(x));
     return d;
 }
@@ -109,12 +132,48 @@ __device__ __forceinline__ uint32_t f16_bits(int s) {
     const _Float16 h = (_Float16)(float)s;
     return (uint32_t)__builtin_bit_cast(uint16_t, h);
 }
+// X4: s 2^-11 as an f16 (a power-of-two scale: the mantissa, and so the low byte, of f16_bits(s))
+__device__ __forceinline__ uint32_t f16_bits_sc(int s) {
+    const _Float16 h = (_Float16)((float)s * (1.0f / 2048.0f));
+    return (uint32_t)__builtin_bit_cast(uint16_t, h);
+}
+// X4, both halves: k 2^-11 -> the 16-bit integer k and back, one packed multiply each and no
+// sub-dword write: k 2^-11 * 2^-13 = k 2^-24, whose f16 pattern IS k for every k < 2048 (below
+// 1024 a subnormal with mantissa k, from 1024 on exponent field 1 and mantissa k - 1024; kernels
+// run with f16 denormals on), and the pattern k times 2^13 is k 2^-11 again.  Above 2047 the
+// pattern stays monotone and >= 2048, all the flag needs (the pair re-runs in int32).
+typedef _Float16 so2_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t sc_to_u16x2(uint32_t x) {
+    const so2_h2 k = {(_Float16)0.0001220703125f, (_Float16)0.0001220703125f};   // 2^-13
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(so2_h2, x) * k);
+}
+__device__ __forceinline__ uint32_t u16x2_to_sc(uint32_t x) {
+    const so2_h2 k = {(_Float16)8192.0f, (_Float16)8192.0f};
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(so2_h2, x) * k);
+}
+// X4: F = max(h + Gap, 0) of both halves (the add's [0, 1] clamp is the floor)
+__device__ __forceinline__ uint32_t pk_addg_clamp(uint32_t h, uint32_t g) {
+    uint32_t d;
+    asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(d) : "v"(h), "s"(g));
+    return d;
+}
+// the words other kernels read, as the 16-bit integers of the integer cell
+template <int FK>
+__device__ __forceinline__ uint32_t so2_out(uint32_t x) {
+    if constexpr (FK == 2) return sc_to_u16x2(x);
+    else if constexpr (FK == 1) return f16x2_to_u16x2(x);
+    else return x;
+}
+// waves per SIMD: the X4 cell at R = 32 holds 3 R registers of state (168-VGPR budget)
+constexpr int so2_waves(int FK, int R) { return FK == 2 && R == 32 ? 3 : 4; }
 
 }  // namespace
 
-template <int ALG, int R, bool FK>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void fill_so2_kernel(FillParams P) {
+template <int ALG, int R, int FK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(so2_waves(FK, R), so2_waves(FK, R))))
+void fill_so2_kernel(FillParams P) {
     constexpr bool NWK = ALG == SA_NW;
+    constexpr bool X4 = FK == 2;   // the 4-op scaled-f16 cell (FK == 1: the 5-op f16 cell)
     static_assert(!(FK && NWK), "the f16 cell is SW's");
     if (sa_skip(P.sel, P.sel_want)) return;   // (the score-only variant has no redo launch)
     static_assert(R >= 8 && R % 2 == 0, "the sampled chunk maximum needs 8 rows per lane");
@@ -178,7 +237,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
             const int s = (int)(int8_t)(so_profile(P.prof[x]) >> (8 * c));
-            if constexpr (FK) w |= (f16_bits(s) >> 8) << (8 * x);
+            if constexpr (X4) w |= (f16_bits_sc(s) >> 8) << (8 * x);
+            else if constexpr (FK) w |= (f16_bits(s) >> 8) << (8 * x);
             else w |= ((uint32_t)(s + 128) & 255u) << (8 * x);
         }
         cw[c] = w;
@@ -201,8 +261,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         __syncthreads();
     }
-    // the column table word of column c of each pair (substitution -128 outside it: 0, FK 0xd8 = -128.0)
-    constexpr uint32_t kOut = FK ? 0xd8d8d8d8u : 0u;
+    // the column table word of column c of each pair (substitution -128 outside it: 0, FK 0xd8 =
+    // -128.0, X4 0xac = -128 / 2048)
+    constexpr uint32_t kOut = X4 ? 0xacacacacu : FK ? 0xd8d8d8d8u : 0u;
     auto col_pair = [&](int c, uint32_t& wa, uint32_t& wb) {
         const bool ia = liveA && c >= 0 && c < nA, ib = liveB && c >= 0 && c < nB;
         uint32_t xa, xb;
@@ -217,7 +278,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         wb = ib ? (xb == 0 ? cw[0] : xb == 1 ? cw[1] : xb == 2 ? cw[2] : cw[3]) : kOut;
     };
     // (FK: the packed f16 Gap)
-    const uint32_t G128 = FK ? f16_bits(G) * 0x10001u : ((uint32_t)(G + 128) & 0xffffu) * 0x10001u;
+    const uint32_t G128 = X4   ? f16_bits_sc(G) * 0x10001u
+                          : FK ? f16_bits(G) * 0x10001u
+                               : ((uint32_t)(G + 128) & 0xffffu) * 0x10001u;
     const uint32_t C128 = 0x00800080u;
 
     typedef uint32_t __attribute__((address_space(1))) gu32;
@@ -230,9 +293,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // and loads take the SGPR-base form and no 64-bit address pair stays live across the chunks)
     const int row0 = (int)band0 * BAND + lane * R;
     uint32_t Hp[R], sel[R];
+    uint32_t Fr[X4 ? R : 1];   // X4: F = max(H + Gap, 0) of the lane's rows at its last column
     uint32_t prev_up = border2(row0), colA = 0, colB = 0, cml = 0, smax = 0;   // (the lane's last row: Hp[R - 1])
 #pragma unroll
     for (int r = 0; r < R; ++r) Hp[r] = border2(row0 + r + 1);
+#pragma unroll
+    for (int r = 0; r < (X4 ? R : 1); ++r) Fr[r] = 0;   // (the left border: max(0 + Gap, 0))
     // NW: H[m][n] of each pair is Hp[rr] of lane L after wavefront step n - 1 + L of the band holding
     // row m - 1 (-1: not this unit's band); cap*: the value, in lane L, took*: this unit's segment
     // holds that step
@@ -281,6 +347,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) Hp[r] = lo16(Hp[r]) | sel[r] << 16;
+        if constexpr (X4) {   // (the hand-off carries H; F follows from it)
+#pragma unroll
+            for (int r = 0; r < R; ++r) Fr[r] = pk_addg_clamp(Hp[r], G128);
+        }
         prev_up = lo16(pa_) | pb_ << 16;
         col_pair((int)(c0 * kChunk) - 1 - lane, colA, colB);
     }
@@ -315,7 +385,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             else
                 asm("v_perm_b32 %1, %2, %3, %4\n\tv_pk_add_u16 %0, %5, %1"
                     : "=&v"(dcur), "=&v"(pt) : "v"(colB), "v"(colA), "v"(sel[0]), "v"(prev_up));
-            uint32_t hu = up;
+            // (X4: the upper input of the lane's first row is F of the row above)
+            uint32_t hu = X4 ? pk_addg_clamp(up, G128) : up;
             // the bias off again: SW with the zero clamp (unsigned saturation), NW without
 #define SO2_CELL_N(LAST)                                                                          \
     asm("v_perm_b32 %[dn], %[cb], %[ca], %[sn]\n\t"                                                \
@@ -347,17 +418,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         "v_pk_maximum3_f16 %[hp], %[t1], %[dr], 0"                                                 \
         : [t1] "=&v"(t1), [hp] "+v"(Hp[r])                                                         \
         : [dr] "v"(dcur), [hu] "v"(hu), [g] "s"(G128))
+#define SO2_CELL_XN                                                                               \
+    asm("v_perm_b32 %[dn], %[cb], %[ca], %[sn]\n\t"                                                \
+        "v_pk_add_f16 %[dn], %[hp], %[dn]\n\t"                                                     \
+        "v_pk_maximum3_f16 %[hp], %[dr], %[fu], %[fl]\n\t"                                         \
+        "v_pk_add_f16 %[fl], %[hp], %[g] clamp"                                                    \
+        : [dn] "=&v"(dn), [hp] "+v"(Hp[r]), [fl] "+v"(Fr[X4 ? r : 0])                              \
+        : [dr] "v"(dcur), [fu] "v"(hu), [g] "s"(G128),                                             \
+          [sn] "v"(sel[r + 1 < R ? r + 1 : r]), [ca] "v"(colA), [cb] "v"(colB))
+#define SO2_CELL_XL                                                                               \
+    asm("v_pk_maximum3_f16 %[hp], %[dr], %[fu], %[fl]\n\t"                                         \
+        "v_pk_add_f16 %[fl], %[hp], %[g] clamp"                                                    \
+        : [hp] "+v"(Hp[r]), [fl] "+v"(Fr[X4 ? r : 0])                                              \
+        : [dr] "v"(dcur), [fu] "v"(hu), [g] "s"(G128))
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                uint32_t t1;
+                [[maybe_unused]] uint32_t t1;
                 if (r + 1 < R) {
                     uint32_t dn;
-                    if constexpr (FK) SO2_CELL_FN;
+                    if constexpr (X4) SO2_CELL_XN;
+                    else if constexpr (FK) SO2_CELL_FN;
                     else if constexpr (NWK) SO2_CELL_N("v_pk_sub_u16 %[hp], %[t1], %[c]");
                     else SO2_CELL_N("v_pk_sub_u16 %[hp], %[t1], %[c] clamp");
                     dcur = dn;
                 } else {
-                    if constexpr (FK) SO2_CELL_FL;
+                    if constexpr (X4) SO2_CELL_XL;
+                    else if constexpr (FK) SO2_CELL_FL;
                     else if constexpr (NWK) SO2_CELL_L("v_pk_sub_u16 %[hp], %[t1], %[c]");
                     else SO2_CELL_L("v_pk_sub_u16 %[hp], %[t1], %[c] clamp");
                 }
@@ -375,8 +461,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                         cml = pk_max_u16(cml, Hp[r]);
                     }
                 }
-                hu = Hp[r];
+                hu = X4 ? Fr[X4 ? r : 0] : Hp[r];
             }
+#undef SO2_CELL_XN
+#undef SO2_CELL_XL
 #undef SO2_CELL_N
 #undef SO2_CELL_L
 #undef SO2_CELL_FN
@@ -438,7 +526,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 }
             }
             if (in) {
-                s_step[ln] = FK ? u16x2_to_f16x2(lo16(ha) | hb << 16) : lo16(ha) | hb << 16;
+                const uint32_t hab = lo16(ha) | hb << 16;
+                s_step[ln] = X4 ? u16x2_to_sc(hab) : FK ? u16x2_to_f16x2(hab) : hab;
                 s_step[32 + 2 * ln] = wa;
                 s_step[33 + 2 * ln] = wb;
             }
@@ -465,11 +554,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             st(std::integral_constant<int, 6>{});
             st(std::integral_constant<int, 7>{});
             const uint32_t po = ((uint32_t)((kC + q0) / SPP) * kWave + (uint32_t)lane) * 16u;
-            if constexpr (FK) {
+            if constexpr (FK != 0) {
 #pragma unroll
                 for (int w = 0; w < SPP / 2; ++w) {
-                    pa[w] = f16x2_to_u16x2(pa[w]);
-                    pb[w] = f16x2_to_u16x2(pb[w]);
+                    pa[w] = so2_out<FK>(pa[w]);
+                    pb[w] = so2_out<FK>(pb[w]);
                 }
             }
             if (liveA) {
@@ -481,7 +570,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 __builtin_nontemporal_store(v4, reinterpret_cast<u32x4*>(dB + po));
             }
         };
-        if (kC < kWave - 1) {   // a band's first chunks: lanes left of their first column wait
+        // (X4 needs no such wait: a lane left of its first column sees H = F = 0 above and to its
+        // left and a substitution <= 0 -- the column words start as 0 -- so its cells stay 0, the
+        // border state; one loop, and no divergent branch around the lane's 3 R state registers)
+        if (!X4 && kC < kWave - 1) {   // a band's first chunks: lanes left of their first column wait
 #pragma unroll 1
             for (int q0 = 0; q0 < kChunk; q0 += SPP) packet(std::true_type{}, q0);
         } else {
@@ -492,7 +584,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t ln = lane_here();
         {
             uint32_t acc = s_step[96 + (ln & 31)];   // lane q < 32: column kC + q - 63
-            if constexpr (FK) acc = f16x2_to_u16x2(acc);
+            acc = so2_out<FK>(acc);
             const int cc = kC + (int)ln - (kWave - 1);
             if (lane < kChunk && cc >= 0) {
                 if ((int)band0 + 1 < BA && cc < nA)
@@ -505,10 +597,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         {
             const uint64_t e = (uint64_t)band0 * P.snap_nch + chunk;
             if (kC + kChunk - 1 < lane) cml = 0;   // (a lane that has not reached its first column)
-            if constexpr (FK) cml = f16x2_to_u16x2(cml);   // (integers from here on)
+            cml = so2_out<FK>(cml);   // (integers from here on)
             smax = pk_max_u16(smax, cml);
             const uint32_t wm = NWK ? 0u : wave_pk_max(cml);
-            const uint32_t pup = FK ? f16x2_to_u16x2(prev_up) : prev_up;
+            const uint32_t pup = so2_out<FK>(prev_up);
             if (liveA && chunk < nchA) {
                 if constexpr (!NWK) {
                     int32_t* const smA = P.snap_m + (uint64_t)sA * P.snap_p_slot + e * kWave;
@@ -520,7 +612,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
                     for (int q = 0; q < R / 2; ++q) {   // (one address, immediate offsets)
                         const uint32_t w = __builtin_amdgcn_perm(Hp[2 * q + 1], Hp[2 * q], 0x05040100u);
-                        sh[q * kWave] = FK ? f16x2_to_u16x2(w) : w;
+                        sh[q * kWave] = so2_out<FK>(w);
                     }
                     int32_t* const spA = P.snap_p + (uint64_t)sA * P.snap_p_slot + e * kWave;
                     spA[ln] = (int32_t)lo16(pup);
@@ -537,7 +629,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
                     for (int q = 0; q < R / 2; ++q) {   // (one address, immediate offsets)
                         const uint32_t w = __builtin_amdgcn_perm(Hp[2 * q + 1], Hp[2 * q], 0x07060302u);
-                        sh[q * kWave] = FK ? f16x2_to_u16x2(w) : w;
+                        sh[q * kWave] = so2_out<FK>(w);
                     }
                     int32_t* const spB = P.snap_p + (uint64_t)sB * P.snap_p_slot + e * kWave;
                     spB[ln] = (int32_t)hi16(pup);
@@ -645,16 +737,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 hipError_t launch_fill_so2(int algo, int R, const FillParams& p, uint32_t grid, hipStream_t stream) {
     const size_t lds = (size_t)kStepBufWords * 4 + 2 * (size_t)p.so2_stage;
 #define SO2_LAUNCH(A, RR, F)                                                                        \
-    if (algo == (A) && R == (RR) && (p.so2_f16 != 0) == (F)) {                                      \
+    if (algo == (A) && R == (RR) && (int)p.so2_f16 == (F)) {                                        \
         hipLaunchKernelGGL((fill_so2_kernel<A, RR, F>), dim3(grid), dim3(kWave), lds, stream, p);  \
         return hipGetLastError();                                                                  \
     }
-    SO2_LAUNCH(SA_SW, 32, true)
-    SO2_LAUNCH(SA_SW, 16, true)
-    SO2_LAUNCH(SA_SW, 32, false)
-    SO2_LAUNCH(SA_SW, 16, false)
-    SO2_LAUNCH(SA_NW, 32, false)
-    SO2_LAUNCH(SA_NW, 16, false)
+    SO2_LAUNCH(SA_SW, 32, 2)
+    SO2_LAUNCH(SA_SW, 16, 2)
+    SO2_LAUNCH(SA_SW, 32, 1)
+    SO2_LAUNCH(SA_SW, 16, 1)
+    SO2_LAUNCH(SA_SW, 32, 0)
+    SO2_LAUNCH(SA_SW, 16, 0)
+    SO2_LAUNCH(SA_NW, 32, 0)
+    SO2_LAUNCH(SA_NW, 16, 0)
 #undef SO2_LAUNCH
     return hipErrorInvalidValue;
 }

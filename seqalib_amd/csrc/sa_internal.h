@@ -109,7 +109,8 @@ struct FillParams {
     // the two-pairs-per-wave SW fill (sa_fill_so2.hip): bytes of LDS per pair for its unit's Seq2
     // symbol codes (0: read from global memory per chunk)
     uint32_t so2_stage;
-    // 1: its f16 cell (SW; every value exact below 2048, pairs above kSo2F16RetryAbove re-run)
+    // its f16 cells (SW; every value exact below 2048, pairs above kSo2F16RetryAbove re-run): 1 the
+    // 5-op cell on f16 integers, 2 the 4-op cell on values scaled by 2^-11 with F kept per row
     uint32_t so2_f16;
 };
 // the f16 cell's retry threshold on (sampled maximum - kSoSlack Gap): below it every value of the

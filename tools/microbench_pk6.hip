@@ -11,6 +11,10 @@
 //   PK4F (V = 4): f16 scaled by 2^-11 so that the add's clamp is the zero floor, and F = max(H + Gap,
 //   0) kept per row beside H: dn = Hd + s, H = v_pk_maximum3_f16(dn, Fu, Fl), F = clamp(H + Gap) --
 //   4 ops per 2 cells, 2R registers of state
+//   PK4F+ (V = 5): PK4F with the per-step extras of fill_so2_kernel's X4 cell -- the upper F of the
+//   lane's first row (one clamped add of the H taken from the lane above), the lane's last row pushed
+//   into the edge packets of both pairs (v_alignbit_b32 + v_perm_b32) and the packets' way out to
+//   16-bit integers (one v_pk_mul_f16 per word of two steps, per pair: one op per step)
 //   PK5F (V = 3): the same cell in f16 -- sub as an f16 whose low byte is 0 (the perm's high byte),
 //   one v_pk_maximum3_f16 takes max(D + s, M + G, 0): 5 ops per 2 cells
 // argv[1] = waves per SIMD (1024 * wps single-wave workgroups).  Cycles are SIMD-cycles per 64
@@ -38,6 +42,7 @@ __global__ __launch_bounds__(64) void cells(const uint32_t* in, uint32_t* out, i
         Hp[r] = 0;
         Fr[r] = 0;
     }
+    [[maybe_unused]] uint32_t recA = 0, recB = 0;
     uint32_t hl = 0, sym = (lane & 3) * 8, prev_up = 0, cml = 0, srcA = 0x7f7f7f81u, srcB = 0x7f817f7fu;
     const uint32_t CU1 = 1;
     const uint32_t G128 = 0x007f007fu, C128 = 0x00800080u;   // packed G + 128 (G = -1), 128
@@ -45,6 +50,7 @@ __global__ __launch_bounds__(64) void cells(const uint32_t* in, uint32_t* out, i
     for (int s = 0; s < steps; ++s) {
         const uint32_t up_h = shr1(in[s & 1023], hl);
         uint32_t hu = up_h, dcur;
+        if constexpr (V == 5) asm volatile("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(hu) : "v"(up_h), "s"(GF16));
         if constexpr (V == 0) {
             sym = shr1((uint32_t)((s * 7) & 3) * 8, sym);
             asm volatile("v_bfe_i32 %0, %1, %2, 8\n\tv_add_u16 %0, %3, %0" : "=&v"(dcur) : "v"(tab[0]), "v"(sym), "v"(prev_up));
@@ -93,7 +99,7 @@ __global__ __launch_bounds__(64) void cells(const uint32_t* in, uint32_t* out, i
                              : [t1] "=&v"(t1), [dn] "=&v"(dn), [hp] "+v"(Hp[r])
                              : [dr] "v"(dcur), [hu] "v"(hu), [g] "s"(GF16), [tabn] "v"(tabn), [sa] "v"(srcA), [sb] "v"(srcB));
                 if (r % 8 == 7 && (s & 3) == 3) asm volatile("v_pk_max_u16 %0, %0, %1" : "+v"(cml) : "v"(Hp[r]));
-            } else if constexpr (V == 4) {
+            } else if constexpr (V == 4 || V == 5) {
                 // PK4F: scaled f16 (H / 2048, clamp = the zero floor), F = max(H + Gap, 0) kept per row:
                 // dn = Hd + s; H = max3(dn, Fu, Fl); F = clamp(H + Gap)
                 asm volatile("v_perm_b32 %[dn], %[sb], %[sa], %[tabn]\n\t"
@@ -121,6 +127,15 @@ __global__ __launch_bounds__(64) void cells(const uint32_t* in, uint32_t* out, i
         }
         prev_up = up_h;
         hl = Hp[R - 1];
+        if constexpr (V == 5) {
+            recA = __builtin_amdgcn_alignbit(hl, recA, 16u);
+            recB = __builtin_amdgcn_perm(hl, recB, 0x07060302u);
+            if (s & 1) {
+                asm volatile("v_pk_mul_f16 %0, %1, %2" : "=v"(recA) : "v"(recA), "s"(0x08000800u));
+                asm volatile("v_pk_mul_f16 %0, %1, %2" : "=v"(recB) : "v"(recB), "s"(0x08000800u));
+                cml ^= recA ^ recB;
+            }
+        }
     }
     uint32_t x = hl ^ cml ^ srcA ^ srcB;
 #pragma unroll
@@ -145,6 +160,8 @@ int main(int argc, char** argv) {
         {"PK5F f16 with maximum3 floor, R16", cells<3, 16>, 32},
         {"PK4F scaled f16, F kept, R16", cells<4, 16>, 32},
         {"PK4F scaled f16, F kept, R32", cells<4, 32>, 64},
+        {"PK4F+ with the kernel's step extras, R16", cells<5, 16>, 32},
+        {"PK4F+ with the kernel's step extras, R32", cells<5, 32>, 64},
     };
     const int steps = 4000;
     for (auto& k : ks) {
