@@ -28,6 +28,18 @@ public:
         return out;
     }
 
+    // Extension: the getScore() of every pair in one GPU pass with no traceback (no AlignedSequence is
+    // built, no op buffer allocated); getScore() afterwards returns the last pair's.
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_HIRSCHBERG, HirschbergSA, ContainerType, Ty>(*this, pairs, res);
+        std::vector<ScoreSystemType> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.push_back(r.score);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+
     // Extension: NW score H[m][n] of the last alignment (the reference exposes none).
     ScoreSystemType getScore() const { return LastScore; }
 };

@@ -35,6 +35,36 @@ public:
         return out;
     }
 
+    // Extensions: scores / end cells of every pair in one GPU pass with no traceback (no
+    // AlignedSequence is built, no op buffer allocated); getScore() / getEndCell() afterwards return
+    // the last pair's.  The three hack sizes report the NW score at (m, n), as getAlignment does.
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        std::vector<sa_result> res;
+        scoreBatch(pairs, res);
+        std::vector<ScoreSystemType> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.push_back(r.score);
+        return out;
+    }
+    std::vector<std::pair<size_t, size_t>> getEndCells(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        std::vector<sa_result> res;
+        scoreBatch(pairs, res);
+        std::vector<std::pair<size_t, size_t>> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.emplace_back((size_t)r.end_i, (size_t)r.end_j);
+        return out;
+    }
+
     ScoreSystemType getScore() const { return MaxScore; }
     std::pair<size_t, size_t> getEndCell() const { return {MaxRow, MaxCol}; }
+
+private:
+    void scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res) {
+        seqalib::detail::run_scores<SA_LOCAL_GOTOH, LocalGotohSA, ContainerType, Ty>(*this, pairs, res);
+        if (!res.empty()) {
+            MaxRow = res.back().end_i;
+            MaxCol = res.back().end_j;
+            MaxScore = res.back().score;
+        }
+    }
 };

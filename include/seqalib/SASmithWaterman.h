@@ -55,7 +55,47 @@ public:
         return out;
     }
 
+    // Extensions: scores / end cells of every pair in one GPU pass with no traceback (no
+    // AlignedSequence is built, no op buffer allocated).  The members move as in getAlignments: a
+    // pair with an empty side scores INT_MIN and keeps the end cell of the pair before it.
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        std::vector<std::pair<size_t, size_t>> cells;
+        return scoreBatch(pairs, cells);
+    }
+    std::vector<std::pair<size_t, size_t>> getEndCells(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        std::vector<std::pair<size_t, size_t>> cells;
+        scoreBatch(pairs, cells);
+        return cells;
+    }
+
     // Extensions (the reference keeps these private): score and end cell of the last alignment.
     ScoreSystemType getScore() const { return MaxScore; }
     std::pair<size_t, size_t> getEndCell() const { return {MaxRow, MaxCol}; }
+
+private:
+    std::vector<ScoreSystemType> scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                            std::vector<std::pair<size_t, size_t>>& cells) {
+        std::vector<std::pair<ContainerType*, ContainerType*>> work;
+        for (auto& p : pairs)
+            if (p.first->size() && p.second->size()) work.push_back(p);
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_SW, SmithWatermanSA, ContainerType, Ty>(*this, work, res);
+        std::vector<ScoreSystemType> out;
+        out.reserve(pairs.size());
+        cells.clear();
+        cells.reserve(pairs.size());
+        size_t k = 0;
+        for (auto& p : pairs) {
+            if (p.first->size() && p.second->size()) {
+                MaxRow = res[k].end_i;
+                MaxCol = res[k].end_j;
+                MaxScore = res[k++].score;
+            } else {
+                MaxScore = std::numeric_limits<ScoreSystemType>::min();
+            }
+            out.push_back(MaxScore);
+            cells.emplace_back(MaxRow, MaxCol);
+        }
+        return out;
+    }
 };

@@ -271,6 +271,18 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
     return out;
 }
 
+// Shared getScores() / getEndCells() body: one score call (no traceback, no AlignedSequence, no op
+// buffers) over the batch; res[p] holds pair p's score and end cell.
+template <int ALGO, typename Aligner, typename ContainerType, typename Ty>
+void run_scores(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                std::vector<sa_result>& res) {
+    auto fn = self.getMatchOperation();
+    const bool has_fn = !(fn == nullptr);
+    const sa_scoring sc = self.getScoring().toC();
+    res.clear();
+    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res);
+}
+
 }  // namespace detail
 }  // namespace seqalib
 

@@ -258,20 +258,21 @@ bool call_match(std::nullptr_t&, bool, const A& x, const A& y) {
 // Generic-Ty path: per-pair m x n match bitmaps, built exactly as the reference's
 // cacheAllMatches builds its match cache (one MatchFnTy call per cell, e.g. SASmithWaterman.h:
 // 20-45; the == operator for a nullptr match fn), packed to bits for sa_align_batch_bits.
-template <typename Ty, typename ContainerType, typename MatchFnTy>
-void align_bits(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
-                const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
-                raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off) {
-    PhaseTimer tm;
+template <typename ContainerType, typename MatchFnTy>
+void match_bitmaps(MatchFnTy& fn, bool has_fn, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                   std::vector<uint64_t>& o1, std::vector<uint64_t>& o2, std::vector<uint64_t>& bo,
+                   std::vector<uint32_t>& bits) {
     const uint32_t np = (uint32_t)pairs.size();
-    std::vector<uint64_t> o1(1, 0), o2(1, 0), bo(1, 0);
+    o1.assign(1, 0);
+    o2.assign(1, 0);
+    bo.assign(1, 0);
     for (auto& p : pairs) {
         const uint64_t m = (uint64_t)p.first->size(), n = (uint64_t)p.second->size();
         o1.push_back(o1.back() + m);
         o2.push_back(o2.back() + n);
         bo.push_back(bo.back() + m * ((n + 31) / 32));
     }
-    std::vector<uint32_t> bits(bo.back() + 1, 0u);
+    bits.assign(bo.back() + 1, 0u);
     for (uint32_t q = 0; q < np; ++q) {
         ContainerType& a = *pairs[q].first;
         ContainerType& b = *pairs[q].second;
@@ -282,6 +283,17 @@ void align_bits(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
                 if (call_match(fn, has_fn, a[i], b[j])) w[i * wn + j / 32] |= 1u << (j % 32);
             }
     }
+}
+
+template <typename Ty, typename ContainerType, typename MatchFnTy>
+void align_bits(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
+                const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
+                raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off) {
+    PhaseTimer tm;
+    const uint32_t np = (uint32_t)pairs.size();
+    std::vector<uint64_t> o1, o2, bo;
+    std::vector<uint32_t> bits;
+    match_bitmaps(fn, has_fn, pairs, o1, o2, bo, bits);
     tm.lap("match bitmaps");
     res.assign(np, sa_result{});
     const uint64_t cap = o1.back() + o2.back() + np + 1;
@@ -338,6 +350,33 @@ void code_symbols(std::false_type, Coder& coder, const std::vector<std::pair<Con
     }
 }
 
+// What align() and score() hand to the C ABI: the pairs' length offsets and their symbols coded into
+// the per-thread packed byte buffers (coder.overflow: more than 256 distinct symbols, bitmap path).
+template <typename Ty>
+struct PackedBatch {
+    SymbolCoder<Ty> coder;
+    std::vector<uint64_t> o1, o2;
+    raw_vector<uint8_t>* s1 = nullptr;
+    raw_vector<uint8_t>* s2 = nullptr;
+};
+template <typename Ty, typename ContainerType>
+void pack_batch(PackedBatch<Ty>& pk, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+    pk.o1.assign(1, 0);
+    pk.o2.assign(1, 0);
+    pk.o1.reserve(pairs.size() + 1);
+    pk.o2.reserve(pairs.size() + 1);
+    for (auto& p : pairs) {
+        pk.o1.push_back(pk.o1.back() + (uint64_t)p.first->size());
+        pk.o2.push_back(pk.o2.back() + (uint64_t)p.second->size());
+    }
+    pk.s1 = &host_buffer(kHostSeq1);   // (+1 below: never a NULL pointer)
+    pk.s2 = &host_buffer(kHostSeq2);
+    pk.s1->resize(pk.o1.back() + 1);
+    pk.s2->resize(pk.o2.back() + 1);
+    constexpr bool kDirect = std::is_integral<Ty>::value && sizeof(Ty) == 1;
+    code_symbols(std::integral_constant<bool, kDirect>{}, pk.coder, pairs, pk.o1, pk.o2, *pk.s1, *pk.s2);
+}
+
 // Aligns a batch of (Seq1, Seq2) pairs on the GPU.  Returns the per-pair results and the op
 // streams (traceback order).  has_fn = false means the reference's nullptr match fn (equality).
 // chunks > 1: the GPU call runs in that many pair ranges (sa_align_batch_cb) and on_chunk(p0, p1)
@@ -352,20 +391,11 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            std::vector<sa_result>& res, raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off,
            uint32_t chunks = 0, ChunkFn on_chunk = nullptr) {
     PhaseTimer tm;
-    SymbolCoder<Ty> coder;
-    std::vector<uint64_t> o1(1, 0), o2(1, 0);
-    o1.reserve(pairs.size() + 1);
-    o2.reserve(pairs.size() + 1);
-    for (auto& p : pairs) {
-        o1.push_back(o1.back() + (uint64_t)p.first->size());
-        o2.push_back(o2.back() + (uint64_t)p.second->size());
-    }
-    raw_vector<uint8_t>& s1 = host_buffer(kHostSeq1);   // (+1 below: never a NULL pointer)
-    raw_vector<uint8_t>& s2 = host_buffer(kHostSeq2);
-    s1.resize(o1.back() + 1);
-    s2.resize(o2.back() + 1);
-    constexpr bool kDirect = std::is_integral<Ty>::value && sizeof(Ty) == 1;
-    code_symbols(std::integral_constant<bool, kDirect>{}, coder, pairs, o1, o2, s1, s2);
+    PackedBatch<Ty> pk;
+    pack_batch(pk, pairs);
+    SymbolCoder<Ty>& coder = pk.coder;
+    std::vector<uint64_t>&o1 = pk.o1, &o2 = pk.o2;
+    raw_vector<uint8_t>&s1 = *pk.s1, &s2 = *pk.s2;
     tm.lap("symbol coding");
     if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
         align_bits<Ty>(algo, sc, fn, has_fn, pairs, res, ops, ops_off);
@@ -401,6 +431,50 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
         if (r.flags & SA_FLAG_TIMEOUT)
             throw std::runtime_error("seqalib: device band hand-off timed out; result invalid");
     }
+}
+
+// Scores a batch of (Seq1, Seq2) pairs on the GPU with no traceback (sa_score_batch*): the
+// dispatch of align() -- byte symbols, or a symbol table of up to 256 symbols, or match bitmaps
+// above that, or the multi-GPU handle -- without an op buffer anywhere.  res[p]: score and end cell
+// of pair p (start = -1, nops = 0).
+template <typename Ty, typename ContainerType, typename MatchFnTy>
+void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
+           const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res) {
+    PhaseTimer tm;
+    PackedBatch<Ty> pk;
+    pack_batch(pk, pairs);
+    SymbolCoder<Ty>& coder = pk.coder;
+    std::vector<uint64_t>&o1 = pk.o1, &o2 = pk.o2;
+    raw_vector<uint8_t>&s1 = *pk.s1, &s2 = *pk.s2;
+    tm.lap("symbol coding");
+    const uint32_t n = (uint32_t)pairs.size();
+    res.assign(n, sa_result{});
+    if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
+        std::vector<uint64_t> bo;
+        std::vector<uint32_t> bits;
+        match_bitmaps(fn, has_fn, pairs, o1, o2, bo, bits);
+        tm.lap("match bitmaps");
+        check(sa_score_batch_bits(context(), algo, &sc, o1.data(), o2.data(), n, bits.data(), bo.data(), res.data()),
+              "sa_score_batch_bits");
+        tm.lap("sa_score_batch_bits (GPU)");
+    } else {
+        std::vector<uint8_t> lut;
+        if (has_fn) lut = build_lut(coder, fn);
+        if (sa_multi* mg = multi_context()) {
+            const int rc = sa_multi_score_batch(mg, algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                                has_fn ? lut.data() : nullptr, res.data());
+            if (rc != SA_OK)
+                throw std::runtime_error(std::string("seqalib: sa_multi_score_batch: ") + sa_status_string(rc) + " (" +
+                                         sa_multi_last_error(mg) + ")");
+        } else {
+            check(sa_score_batch(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                 has_fn ? lut.data() : nullptr, res.data()),
+                  "sa_score_batch");
+        }
+        tm.lap("sa_score_batch (GPU)");
+    }
+    for (auto& r : res)
+        if (r.flags & SA_FLAG_TIMEOUT) throw std::runtime_error("seqalib: device band hand-off timed out; result invalid");
 }
 
 }  // namespace detail

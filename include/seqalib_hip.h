@@ -194,6 +194,44 @@ int sa_align_batch_device(sa_ctx* ctx, int algo, const sa_scoring* scoring,
                           uint32_t max_m, uint32_t max_n, const uint8_t* d_match_lut,
                           sa_result* d_results, uint8_t* d_ops, void* stream);
 
+/* Score-only batch API: the score and the end cell of every pair, with no traceback.  Each call is
+ * its align counterpart (sa_align_batch, sa_align_batch_bits, sa_align_batch_device,
+ * sa_multi_align_batch) without the ops buffer: same arguments, argument checks, status codes,
+ * chunking and threading rules.  Nothing allocates, packs or downloads an op stream and no
+ * traceback kernel is launched.  For every pair it returns the sa_result the align call returns,
+ * except that
+ *   start_i = start_j = -1, nops = 0, reserved = 0;
+ *   SA_FLAG_DIVERGED and SA_FLAG_RECOVERED never appear (they are properties of the walk);
+ *   SA_FLAG_BAD_SHAPE (device API) and SA_FLAG_SIZE_HACK (host API: the three LocalGotoh sizes
+ *   report the NW score, as sa_align_batch does) appear exactly as in the align call.
+ * score, end_i and end_j are bit-exact with the align path: SW / LocalGotoh the last row-major cell
+ * holding the maximum (SW on an empty input: INT32_MIN), NW / GlobalGotoh H[m][n] at (m, n).
+ * SA_HIRSCHBERG is accepted and means NW (its score is NW's H[m][n]); SA_MYERS_MILLER returns
+ * SA_ERR_UNSUPPORTED (its score is defined by its own recursion).
+ * Batches on the int32 kernels (LUT match functions, more than 4 distinct symbols, bitmaps,
+ * !AllowMismatch, scorings beyond 16 bits) run a fill that stores nothing for a traceback
+ * (SA_RECORDS_NONE): a pair's workspace is then its row buffer, O(n), so far more pairs fit one
+ * launch and a pair whose records would exceed sa_set_workspace_limit still scores.  DNA batches
+ * keep the T16 / score-only fills and their end-cell replay, and only skip the walks.
+ * The device call works with sa_set_pipeline, interleaved with pipelined align calls.  After a
+ * score call sa_last_timings reports traceback_ms = 0. */
+int sa_score_batch(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                   const uint8_t* seq1, const uint64_t* seq1_off,
+                   const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                   const uint8_t* match_lut, sa_result* results);
+int sa_score_batch_bits(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                        const uint64_t* seq1_off, const uint64_t* seq2_off, uint32_t npairs,
+                        const uint32_t* match_bits, const uint64_t* bits_off, sa_result* results);
+int sa_score_batch_device(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                          const uint8_t* d_seq1, const uint64_t* d_seq1_off,
+                          const uint8_t* d_seq2, const uint64_t* d_seq2_off, uint32_t npairs,
+                          uint32_t max_m, uint32_t max_n, const uint8_t* d_match_lut,
+                          sa_result* d_results, void* stream);
+int sa_multi_score_batch(sa_multi* multi, int algo, const sa_scoring* scoring,
+                         const uint8_t* seq1, const uint64_t* seq1_off,
+                         const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                         const uint8_t* match_lut, sa_result* results);
+
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events
  * recorded on the stream they ran on: total fill-kernel ms, total traceback-kernel ms, and the
  * number of fill launches.  Waits for those events. */
@@ -224,6 +262,7 @@ int sa_last_plan(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves);
 #define SA_RECORDS_FLAGS 0
 #define SA_RECORDS_TAGS 1
 #define SA_RECORDS_SCORE_ONLY 2
+#define SA_RECORDS_NONE 3   /* score calls on the int32 / small-call kernels: the fill stored nothing for a traceback */
 int sa_last_plan_ex(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves, int* records);
 
 /* Plan of the int32 kernel for a batch (host-only query, no device needed): rows per lane R,
@@ -243,6 +282,16 @@ int sa_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t npairs,
 int sa_plan_query_ex(int algo, const sa_scoring* scoring, uint32_t max_m, uint32_t max_n,
                      uint32_t npairs, int nsym, int* kernel, int* rows_per_lane, int* waves,
                      uint64_t* workspace_bytes_per_pair);
+
+/* sa_plan_query_ex for a score call (host-only query, no device needed): the kernel a host score
+ * call (sa_score_batch) runs when the batch holds `nsym` distinct symbols, its R and W, and the
+ * device workspace one pair occupies.  With nsym > 4, or a scoring that does not admit T16, that is
+ * the record-free int32 fill: row buffers only, no direction records.  With nsym <= 4 it is the
+ * align call's plan (the T16 / score-only fills keep their edge streams and snapshots for the
+ * end-cell replay).  SA_HIRSCHBERG means NW; SA_MYERS_MILLER: SA_ERR_UNSUPPORTED. */
+int sa_score_plan_query(int algo, const sa_scoring* scoring, uint32_t max_m, uint32_t max_n,
+                        uint32_t npairs, int nsym, int* kernel, int* rows_per_lane, int* waves,
+                        uint64_t* workspace_bytes_per_pair);
 
 /* Tests only (tests/test_gpu_robust.py).  SA_HOOK_HAND_TAG: the band-unit hand-off tag of the
  * context's last launch becomes `value` (0..65535; the next launch takes value + 1, and at 65535 the

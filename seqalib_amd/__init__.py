@@ -11,7 +11,9 @@ benchmark and Python users:
   :class:`GlobalGotohSA` — ``getAlignment(seq1, seq2)`` returns an :class:`AlignedSequence`
   exactly like the reference's (``SASmithWaterman.h:358-366`` etc.); ``getAlignments`` aligns a
   batch in one GPU pass.
-* :class:`Engine` — the batch C ABI (host or device-resident buffers).
+* :class:`Engine` — the batch C ABI (host or device-resident buffers), align calls and the
+  score-only calls (``score*``: scores and end cells, no traceback); ``getScores`` / ``getEndCells``
+  on the aligner classes.
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present, calls fail with
 :class:`SeqalibError`.
@@ -31,6 +33,7 @@ __all__ = [
     "SmithWatermanSA", "NeedlemanWunschSA", "LocalGotohSA", "GlobalGotohSA", "HirschbergSA", "MyersMillerSA",
     "load_library", "library_path", "expand_ops", "synth_dna", "synth_mutate", "synth_dna_batch",
     "SA_FLAG_DIVERGED", "SA_FLAG_BAD_SHAPE", "SA_FLAG_SIZE_HACK", "SA_FLAG_TIMEOUT",
+    "SA_RECORDS_NONE", "score_plan_query",
 ]
 
 SA_SW, SA_NW, SA_LOCAL_GOTOH, SA_GLOBAL_GOTOH, SA_HIRSCHBERG, SA_MYERS_MILLER = 0, 1, 2, 3, 4, 5
@@ -40,6 +43,7 @@ SA_FLAG_DIVERGED, SA_FLAG_BAD_SHAPE, SA_FLAG_SIZE_HACK, SA_FLAG_TIMEOUT = 1, 2, 
 SA_KERNEL_INT32, SA_KERNEL_T16, SA_KERNEL_T16_ENDCELL, SA_KERNEL_TINY = 0, 1, 2, 3
 SA_PIPELINE_DEPTH = 2   # pipelined device calls that may run at once (distinct output buffers)
 SA_RECORDS_FLAGS, SA_RECORDS_TAGS, SA_RECORDS_SCORE_ONLY = 0, 1, 2
+SA_RECORDS_NONE = 3   # score calls on the int32 / small-call kernels: nothing stored for a traceback
 SA_HOOK_HAND_TAG, SA_HOOK_POISON_WS, SA_HOOK_F16 = 1, 2, 3   # sa_test_hook (tests only)
 INT32_MIN = -(2 ** 31)
 
@@ -126,6 +130,13 @@ def load_library():
                                       C.c_uint64]
     L.sa_align_batch_device.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32,
                                         C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_score_batch.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sa_multi_score_batch.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.sa_score_batch_bits.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, C.c_uint32, vp, vp, vp]
+    L.sa_score_batch_device.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32,
+                                        C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_score_plan_query.argtypes = [C.c_int, C.POINTER(_Scoring), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                      i32p, i32p, i32p, u64p]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
     L.sa_last_kernel_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sa_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p, u64p]
@@ -140,7 +151,8 @@ def load_library():
     L.sa_synth_mutate.argtypes = [vp, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.sa_synth_dna_batch.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_int]
     for fn in ("sa_set_workspace_limit", "sa_trim", "sa_align_batch", "sa_align_batch_bits", "sa_align_batch_device",
-               "sa_multi_create", "sa_multi_align_batch",
+               "sa_multi_create", "sa_multi_align_batch", "sa_score_batch", "sa_score_batch_bits",
+               "sa_score_batch_device", "sa_multi_score_batch", "sa_score_plan_query",
                "sa_last_timings", "sa_last_kernel_timings", "sa_last_plan", "sa_last_plan_ex", "sa_plan_query", "sa_plan_query_ex", "sa_synth_dna", "sa_synth_mutate", "sa_synth_dna_batch",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
@@ -477,6 +489,68 @@ class Engine:
                                           max_n, d_lut or None, d_res, d_ops, stream or None)
         self._check(rc, "sa_align_batch_device")
 
+    # ---- score-only calls: scores and end cells, no traceback (include/seqalib_hip.h sa_score_batch)
+    def score_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                     s2: np.ndarray, off2: np.ndarray, lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host-buffer score batch (sa_score_batch): the results structured array (start = -1,
+        nops = 0); no op buffer exists anywhere."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_score_batch(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                   npairs, lut_p, _ptr(res))
+        self._check(rc, "sa_score_batch")
+        return res[:npairs]
+
+    def score_bits(self, algo: int, scoring: ScoringSystem, off1: np.ndarray, off2: np.ndarray, bits: np.ndarray,
+                   bits_off: np.ndarray) -> np.ndarray:
+        """Generic-Ty score batch (sa_score_batch_bits) from match_bitmaps(): the results array."""
+        npairs = len(off1) - 1
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        bits_off = np.ascontiguousarray(bits_off, dtype=np.uint64)
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        sc = scoring._c()
+        rc = self.L.sa_score_batch_bits(self.h, algo, C.byref(sc), _ptr(off1), _ptr(off2), npairs, _ptr(bits),
+                                        _ptr(bits_off), _ptr(res))
+        self._check(rc, "sa_score_batch_bits")
+        return res[:npairs]
+
+    @staticmethod
+    def _score_results(res: np.ndarray) -> List[PairResult]:
+        return [PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]), int(r["start_j"]),
+                           int(r["flags"]), b"") for r in res]
+
+    def score_generic(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[Sequence, Sequence]],
+                      match: Optional[Callable] = None) -> List[PairResult]:
+        """score() for pairs of sequences of any symbol type with any match predicate (match bitmaps)."""
+        off1, off2, bits, bits_off = match_bitmaps(pairs, match)
+        return self._score_results(self.score_bits(algo, scoring, off1, off2, bits, bits_off))
+
+    def score(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]],
+              lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """Scores and end cells of a batch; PairResult.ops is b"", start_i = start_j = -1."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_packed(algo, scoring, s1, off1, s2, off2, lut))
+
+    def score_device(self, algo: int, scoring: ScoringSystem, d_s1: int, d_off1: int, d_s2: int, d_off2: int,
+                     npairs: int, max_m: int, max_n: int, d_res: int, stream: int = 0, d_lut: int = 0):
+        """Device-resident score batch (sa_score_batch_device); pointers are device addresses.  Works
+        with set_pipeline(True), interleaved with align_device calls."""
+        sc = scoring._c()
+        rc = self.L.sa_score_batch_device(self.h, algo, C.byref(sc), d_s1, d_off1, d_s2, d_off2, npairs, max_m,
+                                          max_n, d_lut or None, d_res, stream or None)
+        self._check(rc, "sa_score_batch_device")
+
     def set_pipeline(self, enable: bool):
         """Overlap consecutive align_device calls (sa_set_pipeline); results need wait()."""
         self._check(self.L.sa_set_pipeline(self.h, 1 if enable else 0), "sa_set_pipeline")
@@ -542,6 +616,19 @@ def plan_query_ex(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, n
                             C.byref(ws))
     if rc:
         raise SeqalibError("sa_plan_query_ex failed")
+    return k.value, R.value, W.value, ws.value
+
+
+def score_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 4):
+    """plan_query_ex for a host score call (sa_score_plan_query): with nsym > 4 the record-free int32
+    fill, whose workspace per pair holds no direction records.  SA_MYERS_MILLER raises."""
+    L = load_library()
+    k, R, W, ws = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+    sc = scoring._c()
+    rc = L.sa_score_plan_query(algo, C.byref(sc), max_m, max_n, npairs, nsym, C.byref(k), C.byref(R), C.byref(W),
+                               C.byref(ws))
+    if rc:
+        raise SeqalibError(f"sa_score_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
     return k.value, R.value, W.value, ws.value
 
 
@@ -634,8 +721,27 @@ class _Aligner:
     def getScore(self) -> Optional[int]:
         return None if self.last is None else self.last.score
 
+    def _score_results(self, pairs) -> List[PairResult]:
+        res = _engine(self.device).score(self.ALGO, self.scoring, pairs, self._lut(pairs))
+        for r in res:
+            if r.flags & SA_FLAG_TIMEOUT:
+                raise SeqalibError("device hand-off timed out; result invalid")
+        self.last = res[-1] if res else None
+        return res
 
-class SmithWatermanSA(_Aligner):
+    def getScores(self, pairs: Sequence[Tuple[object, object]]) -> List[int]:
+        """The getScore() of every pair in one GPU pass with no traceback; getScore() afterwards is
+        the last pair's."""
+        return [r.score for r in self._score_results(pairs)]
+
+
+class _LocalAligner(_Aligner):
+    def getEndCells(self, pairs: Sequence[Tuple[object, object]]) -> List[Tuple[int, int]]:
+        """(MaxRow, MaxCol) of every pair -- the last row-major cell holding the maximum."""
+        return [(r.end_i, r.end_j) for r in self._score_results(pairs)]
+
+
+class SmithWatermanSA(_LocalAligner):
     ALGO = SA_SW
 
     @staticmethod
@@ -647,7 +753,7 @@ class NeedlemanWunschSA(_Aligner):
     ALGO = SA_NW
 
 
-class LocalGotohSA(_Aligner):
+class LocalGotohSA(_LocalAligner):
     ALGO = SA_LOCAL_GOTOH
 
 

@@ -107,6 +107,10 @@ struct sa_ctx {
     // I/O cache and the DC buffers.
     hipEvent_t ev_last = nullptr;
     bool ev_last_set = false;
+    // kernels the last call launched after its fills' end (ev[1]): walks, the segmented traceback,
+    // the SPLIT fallback behind them.  A score call launches none, and sa_last_timings then reports
+    // traceback_ms = 0 instead of the few microseconds between two event records
+    int tb_kernels = 0;
 };
 
 namespace {
@@ -245,14 +249,25 @@ struct Variant {
     uint64_t seg_slot = 0;    // their hand-off words per pair (FillParams::seg_hand)
     uint64_t snap_c_slot = 0; // score-only SW: 32-bit (band, chunk) maxima per pair (FillParams::snap_c)
     bool so2 = false;         // score-only SW with two pairs per wave (sa_fill_so2.hip)
+    bool norec = false;       // score calls, int32: the record-free fill, no direction slot
     uint64_t slot_bytes = 0;
     int kernel = SA_KERNEL_INT32;
 };
 
-Variant make_variant(int algo, uint32_t max_m, uint32_t max_n, uint32_t npairs, bool t16, bool allow_split) {
+// notb: a score call (no traceback).  Its int32 variant runs the record-free fill and has no
+// direction slot; the T16 variants are the align call's (their end-cell replay reads the snapshots
+// and the edge stream).
+Variant make_variant(int algo, uint32_t max_m, uint32_t max_n, uint32_t npairs, bool t16, bool allow_split,
+                     bool notb = false) {
     Variant v;
     v.t16 = t16;
     v.pl = make_plan(algo, max_m, max_n, npairs, t16, allow_split);
+    if (notb && !t16) {
+        v.norec = true;
+        v.pl.g.dir_slot = 0;
+        v.pl.g.band_stride = 0;
+        if (v.pl.R >= 8 && v.pl.W > 8) v.pl.W = 8;   // kNorecWideThreads (sa_fill_impl.h)
+    }
     // CMAX end-cell tracking (sa_fill_impl.h / sa_endcell.hip): T16 SW on one-wave plans with an
     // end-cell replay instantiation (R <= 32)
     v.cmax = t16 && v.pl.W == 1 && v.pl.R >= 2 &&
@@ -707,13 +722,13 @@ T16Mode t16_candidate(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t m
 // only: 0 both variants (as above), 1 the T16 variant alone, 2 the int32 variant alone (the host
 // decided the batch alphabet itself and T16 provably needs no int32 re-run, run_device).
 int build_variants(int algo, uint32_t max_m, uint32_t max_n, uint32_t npairs, bool t16, Variant (&vars)[3],
-                   bool* has_fb, int only = 0) {
+                   bool* has_fb, int only = 0, bool notb = false) {
     int nv = 0;
-    if (t16 && only != 2) vars[nv++] = make_variant(algo, max_m, max_n, npairs, true, true);
-    if (!t16 || only != 1) vars[nv++] = make_variant(algo, max_m, max_n, npairs, false, true);
+    if (t16 && only != 2) vars[nv++] = make_variant(algo, max_m, max_n, npairs, true, true, notb);
+    if (!t16 || only != 1) vars[nv++] = make_variant(algo, max_m, max_n, npairs, false, true, notb);
     *has_fb = false;
     for (int k = 0; k < nv; ++k) *has_fb = *has_fb || vars[k].pl.split;
-    if (*has_fb) vars[nv] = make_variant(algo, max_m, max_n, npairs, false, false);
+    if (*has_fb) vars[nv] = make_variant(algo, max_m, max_n, npairs, false, false, notb);
     const int all = nv + (*has_fb ? 1 : 0);
     uint64_t dir_stride = 0;
     for (int k = 0; k < all; ++k) dir_stride = std::max(dir_stride, vars[k].pl.g.dir_slot);
@@ -793,14 +808,19 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                const uint8_t* d2, const uint64_t* o2, uint32_t npairs, uint32_t max_m,
                uint32_t max_n, const uint32_t* d_lutbits, sa_result* d_res, uint8_t* d_ops,
                hipStream_t stream, bool pipe = false, const uint32_t* d_mbits = nullptr,
-               const uint64_t* d_mbits_off = nullptr, const HostSeqs* hs = nullptr) {
+               const uint64_t* d_mbits_off = nullptr, const HostSeqs* hs = nullptr, bool notb = false,
+               bool many_syms = false) {
+    // notb: a score call -- the fills, the end-cell replays and score_finish on the fill stream,
+    // nothing on the traceback stream (d_ops is NULL).  many_syms: the caller knows the batch holds
+    // more than 4 distinct symbols, so T16 is no candidate and the int32 variant runs alone.
     if (max_m >= (1u << 24) || max_n >= (1u << 24))
         return fail(c, SA_ERR_UNSUPPORTED, "sequence lengths must be < 2^24");
+    c->tb_kernels = 0;
     const bool keyed = keyed_ok(algo, sc, max_m, max_n);
     const bool allow = sc->allow_mismatch != 0;
     const bool bits = d_mbits != nullptr;   // generic-Ty path: per-pair match bitmaps
     const bool lut = !bits && d_lutbits != nullptr;
-    const T16Mode tm = bits ? T16Mode{} : t16_candidate(algo, sc, max_m, max_n, npairs);
+    const T16Mode tm = (bits || many_syms) ? T16Mode{} : t16_candidate(algo, sc, max_m, max_n, npairs);
     const bool t16 = tm.ok;
     const bool kernel_timing = getenv("SEQALIB_KERNEL_TIMING") != nullptr;
     if (!c->aux) SA_HIP(c, hipMalloc(&c->aux, kPipeSlots * kAuxWords * 4));
@@ -875,7 +895,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
     }
     Variant vars[3];
     bool has_fb = false;
-    const int nv = build_variants(algo, max_m, max_n, npairs, t16, vars, &has_fb, only);
+    const int nv = build_variants(algo, max_m, max_n, npairs, t16, vars, &has_fb, only, notb);
     if (const char* e = getenv("SEQALIB_SPLIT_FALLBACK")) has_fb = has_fb && e[0] != '0';   // tests only
     c->nvar = nv;
     uint64_t slot_bytes = 0, sp_bands = 0;
@@ -885,7 +905,9 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             c->var_kernel[k] = vars[k].kernel;
             c->var_R[k] = vars[k].pl.R;
             c->var_W[k] = vars[k].pl.split ? 0 : vars[k].pl.W;   // 0: SPLIT plan (one single-wave workgroup per band)
-            c->var_records[k] = vars[k].so ? SA_RECORDS_SCORE_ONLY : vars[k].t16 ? SA_RECORDS_TAGS : SA_RECORDS_FLAGS;
+            c->var_records[k] = vars[k].norec ? SA_RECORDS_NONE
+                              : vars[k].so  ? SA_RECORDS_SCORE_ONLY
+                              : vars[k].t16 ? SA_RECORDS_TAGS : SA_RECORDS_FLAGS;
         }
         slot_bytes = std::max(slot_bytes, vars[k].slot_bytes);
         if (vars[k].pl.split) {
@@ -926,7 +948,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
     const uint64_t sp_gran = any_split ? per_launch * sp_bands * std::max<uint32_t>(max_n, 1) * aff2 : 0;
     const uint64_t sp_vblk = (256 + sp_gran * 8 + 255) & ~(uint64_t)255;
     const uint64_t sp_part = (uint64_t)nv * sp_vblk;
-    const int seg_mode = any_split && tb_wave((uint32_t)per_launch) ? tb_seg_mode() : 0;
+    const int seg_mode = any_split && !notb && tb_wave((uint32_t)per_launch) ? tb_seg_mode() : 0;
     // tests only: SEQALIB_SPLIT_WAIT_TICKS shortens the SPLIT bands' bounded wait (forces timeouts
     // and the fallback); SEQALIB_SEG_INJECT=1 overwrites the segmented traceback's exit records
     // between its two kernels (forces its consistency guards and the serial re-walk)
@@ -1087,6 +1109,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             FillVariant fv{pl.R, lut, allow || v.t16, keyed, v.t16, v.cmax, pl.split, bits};
             fv.so = v.so;
             fv.so2 = v.so2;
+            fv.norec = v.norec;
             return fv;
         };
         // Pipelined calls: the int32 variant of a T16 batch (it re-runs only the pairs the T16 fill
@@ -1095,7 +1118,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
         // workgroups waited for the next call's fill to be dispatched (up to 9.6 ms, round 4 rocprof)
         // and delayed the slot's release to the call after it.  It then walks before the T16 variant,
         // so the pairs it re-ran are handed over by flags (TbParams::keep_redo / clear_redo).
-        const bool tb_on_fill = pipe && nv == 2 && !vars[1].t16 && !vars[1].pl.split;
+        const bool tb_on_fill = !notb && pipe && nv == 2 && !vars[1].t16 && !vars[1].pl.split;
         auto make_tp = [&](int k) {
             const Variant& v = vars[k];
             TbParams tp{};
@@ -1143,7 +1166,8 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             const bool units = v.so && !is_affine(algo);
             const uint32_t grid = pl.split ? (uint32_t)(cnt * sp_bands)
                                 : units ? (v.so2 ? (cnt + 1) / 2 : cnt) * pl.g.bands * v.segs : cnt;
-            hipError_t e = v.so2 ? launch_fill_so2(algo, pl.R, fp, grid, sf) : launch_fill(algo, fv, fp, grid, sf);
+            hipError_t e = v.so2 ? launch_fill_so2(algo, pl.R, fp, grid, sf)
+                         : v.norec ? launch_fill_score(algo, fv, fp, grid, sf) : launch_fill(algo, fv, fp, grid, sf);
             if (e != hipSuccess) return hip_fail(c, e, "fill kernel launch");
             if (kev) SA_HIP(c, hipEventRecord(kev[2 * k + 1], sf));
             if (pl.split) {
@@ -1196,11 +1220,27 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                 const TbParams tp = make_tp(k);
                 e = tb_wave(cnt) ? launch_traceback_wave(algo, pl.R, lut, tp, sf) : launch_traceback(algo, pl.R, lut, tp, sf);
                 if (e != hipSuccess) return hip_fail(c, e, "traceback kernel launch");
+                ++c->tb_kernels;
             }
+        }
+        if (notb) {
+            // A score call ends here, on the fill stream: the SPLIT fallback re-fills the pairs flagged
+            // SA_FLAG_TIMEOUT (no walk read their records, so it need not wait for one), then
+            // score_finish does the walks' bookkeeping.  The traceback stream gets no kernel: it only
+            // takes the events below, so the slot's release (ev_slot) still follows this call's last
+            // kernel and the next pipelined call on the slot waits for it as for any other.
+            if (has_fb) {
+                if (vars[nv].pl.split) return fail(c, SA_ERR_UNSUPPORTED, "internal: SPLIT fallback plan");
+                const FillVariant fv = make_fp(nv);
+                hipError_t e = launch_fill_score(algo, fv, fps[nv], cnt, sf);
+                if (e != hipSuccess) return hip_fail(c, e, "fallback fill kernel launch");
+            }
+            hipError_t e = launch_score_finish(d_res, (uint32_t)base, cnt, sf);
+            if (e != hipSuccess) return hip_fail(c, e, "score finish kernel launch");
         }
         SA_HIP(c, hipEventRecord(ev[1], sf));
         if (pipe) SA_HIP(c, hipStreamWaitEvent(stb, ev[1], 0));
-        for (int k = 0; k < nv; ++k) {
+        for (int k = 0; k < nv && !notb; ++k) {
             const Variant& v = vars[k];
             if (tb_on_fill && k == 1) continue;   // walked on the fill stream (above)
             TbParams tp = make_tp(k);
@@ -1215,13 +1255,15 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                 SA_HIP(c, hipMemsetAsync(tp.seg_fin, 0xff, (uint64_t)cnt * 16, stb));
                 hipError_t e = launch_traceback_seg(algo, v.pl.R, lut, tp, stb, seg_inject);
                 if (e != hipSuccess) return hip_fail(c, e, "segmented traceback kernel launch");
+                ++c->tb_kernels;
             }
             hipError_t e = v.so ? launch_traceback_so(algo, v.pl.R, tp, stb)
                          : tb_wave(cnt) ? launch_traceback_wave(algo, v.pl.R, lut, tp, stb)
                                         : launch_traceback(algo, v.pl.R, lut, tp, stb);
             if (e != hipSuccess) return hip_fail(c, e, "traceback kernel launch");
+            ++c->tb_kernels;
         }
-        if (has_fb) {
+        if (has_fb && !notb) {
             if (vars[nv].pl.split) return fail(c, SA_ERR_UNSUPPORTED, "internal: SPLIT fallback plan");
             // SPLIT fallback, after every traceback of this launch (it rewrites the records of the
             // pairs it re-runs): fill + traceback of exactly the pairs flagged SA_FLAG_TIMEOUT,
@@ -1233,6 +1275,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             e = tb_wave(cnt) ? launch_traceback_wave(algo, vars[nv].pl.R, lut, tp, stb)
                              : launch_traceback(algo, vars[nv].pl.R, lut, tp, stb);
             if (e != hipSuccess) return hip_fail(c, e, "fallback traceback kernel launch");
+            c->tb_kernels += 2;
         }
         SA_HIP(c, hipEventRecord(ev[2], stb));
         c->launches++;
@@ -1273,9 +1316,10 @@ bool lg_size_hack(uint64_t m, uint64_t n) {  // SALocalGotoh.h:484-488
 // ScoringSystem (SALocalGotoh.h:484-488).  Split them out, align them with NW, merge back.
 // align_subset(algo, sel, o1, o2, r, op, cap) aligns pairs sel (o1/o2: their packed length
 // offsets) into r / op (op of the q-th selected pair at o1[q] + o2[q] + q).
+// notb (score calls): ops is NULL and no op buffer is allocated or copied.
 template <typename AlignSubset>
 int lg_hack_split(sa_ctx* c, const uint64_t* off1, const uint64_t* off2, uint32_t npairs, sa_result* results,
-                  uint8_t* ops, uint64_t ops_cap, AlignSubset align_subset) {
+                  uint8_t* ops, uint64_t ops_cap, AlignSubset align_subset, bool notb = false) {
     std::vector<uint32_t> hack, keep;
     for (uint32_t p = 0; p < npairs; ++p)
         (lg_size_hack(off1[p + 1] - off1[p], off2[p + 1] - off2[p]) ? hack : keep).push_back(p);
@@ -1284,7 +1328,7 @@ int lg_hack_split(sa_ctx* c, const uint64_t* off1, const uint64_t* off2, uint32_
         return align_subset(SA_LOCAL_GOTOH, keep, o1, o2, results, ops, ops_cap);
     }
     const uint64_t ops_total = off1[npairs] + off2[npairs] + npairs;
-    if (ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer too small");
+    if (!notb && ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer too small");
     for (int pass = 0; pass < 2; ++pass) {
         const std::vector<uint32_t>& sel = pass == 0 ? keep : hack;
         if (sel.empty()) continue;
@@ -1295,14 +1339,15 @@ int lg_hack_split(sa_ctx* c, const uint64_t* off1, const uint64_t* off2, uint32_
         }
         const uint32_t k = (uint32_t)sel.size();
         std::vector<sa_result> r(k);
-        std::vector<uint8_t> op(o1.back() + o2.back() + k + 1);
-        const int rc = align_subset(pass == 0 ? SA_LOCAL_GOTOH : SA_NW, sel, o1, o2, r.data(), op.data(), op.size());
+        std::vector<uint8_t> op(notb ? 0 : o1.back() + o2.back() + k + 1);
+        const int rc = align_subset(pass == 0 ? SA_LOCAL_GOTOH : SA_NW, sel, o1, o2, r.data(), notb ? nullptr : op.data(),
+                                    op.size());
         if (rc) return rc;
         for (uint32_t q = 0; q < k; ++q) {
             const uint32_t p = sel[q];
             results[p] = r[q];
             if (pass == 1) results[p].flags |= SA_FLAG_SIZE_HACK;
-            memcpy(ops + off1[p] + off2[p] + p, op.data() + o1[q] + o2[q] + q, r[q].nops);
+            if (!notb) memcpy(ops + off1[p] + off2[p] + p, op.data() + o1[q] + o2[q] + q, r[q].nops);
         }
     }
     return SA_OK;
@@ -1486,8 +1531,9 @@ constexpr uint64_t kTinyOut = 128ull << 10, kTinyIo = 256ull << 10;
 
 int align_tiny(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
-               sa_result* results, uint8_t* ops, int max_m) {
+               sa_result* results, uint8_t* ops, int max_m, bool notb = false) {
     const bool timing = getenv("SEQALIB_HOST_TIMING") != nullptr;
+    c->tb_kernels = 0;   // (one kernel, no fill launch: sa_last_timings reports zeros)
     const auto t0 = std::chrono::steady_clock::now();
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::micro>(b - a).count();
@@ -1542,14 +1588,14 @@ int align_tiny(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
     tp.gap_extend = sc->gap_extend;
     tp.allow = sc->allow_mismatch;
     const auto t_stage = std::chrono::steady_clock::now();
-    SA_HIP(c, launch_tiny(algo, use_lut, max_m, tp, c->stream));
+    SA_HIP(c, launch_tiny(algo, use_lut, max_m, tp, c->stream, notb));
     const auto t_launch = std::chrono::steady_clock::now();
     SA_HIP(c, hipStreamSynchronize(c->stream));
     const auto t_sync = std::chrono::steady_clock::now();
     const sa_result* hres = reinterpret_cast<const sa_result*>(h + kTinyOut);
     const uint8_t* hops = h + kTinyOut + al(sizeof(sa_result) * npairs);
     memcpy(results, hres, sizeof(sa_result) * npairs);
-    for (uint32_t p = 0; p < npairs; ++p) {
+    for (uint32_t p = 0; p < npairs && !notb; ++p) {
         const uint64_t o = off1[p] + off2[p] + p;
         memcpy(ops + o, hops + o, results[p].nops);
     }
@@ -1559,7 +1605,7 @@ int align_tiny(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
     c->var_kernel[0] = SA_KERNEL_TINY;
     c->var_R[0] = max_m > kWave ? 4 : 1;
     c->var_W[0] = 1;
-    c->var_records[0] = SA_RECORDS_FLAGS;
+    c->var_records[0] = notb ? SA_RECORDS_NONE : SA_RECORDS_FLAGS;
     c->launches = 0;
     c->kvars.clear();
     if (timing)
@@ -1573,7 +1619,10 @@ int align_tiny(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
 int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
                sa_result* results, uint8_t* ops, uint64_t ops_cap, uint32_t chunks = 0,
-               sa_chunk_cb cb = nullptr, void* cb_user = nullptr) {
+               sa_chunk_cb cb = nullptr, void* cb_user = nullptr, bool notb = false) {
+    // notb (sa_score_batch): ops is NULL; no op region is sized, packed or downloaded (ops_total = 0);
+    // the 2-bit sequence pieces land in a zone of their own size (an align call lends them its
+    // packed-ops region)
     // $SEQALIB_HOST_TIMING: host-side phases of the call (stderr)
     const bool timing = getenv("SEQALIB_HOST_TIMING") != nullptr;
     const auto t_call = std::chrono::steady_clock::now();
@@ -1584,12 +1633,12 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
     const uint64_t t1 = off1[npairs], t2 = off2[npairs];
     for (uint32_t p = 0; p < npairs; ++p)
         if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
-    const uint64_t ops_total = t1 + t2 + npairs;
+    const uint64_t ops_total = notb ? 0 : t1 + t2 + npairs;
     if (ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer needs " + std::to_string(ops_total) + " bytes");
     if (!npairs) return SA_OK;
     int tiny_m = 0;
     if (chunks <= 1 && tiny_call(algo, off1, off2, npairs, &tiny_m)) {
-        const int rc = align_tiny(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, tiny_m);
+        const int rc = align_tiny(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, tiny_m, notb);
         if (rc == SA_OK && cb) cb(cb_user, 0, npairs);
         return rc;
     }
@@ -1616,14 +1665,17 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
     const bool small = G == 1 && t1 + t2 <= kHostScanBytes && b_s1 + b_s2 + 2 * b_o <= kSmallCall &&
                        b_res + ops_total <= kSmallCall;
     // other one-chunk calls download their op streams packed (ops_scan / ops_pack): [cpos][packed]
-    const bool packed = G == 1 && !small && !dc;
-    const uint64_t b_cpos = packed ? al(8ull * (npairs + 1)) : 0, b_pack = packed ? b_ops : 0;
+    const bool packed = G == 1 && !small && !dc && !notb;
+    const uint64_t b_cpos = packed ? al(8ull * (npairs + 1)) : 0;
     // 2-bit transfers (sa_codec.cpp; $SEQALIB_XFER2=0 sends bytes): sequence pieces land in the
     // packed-ops region (free until the traceback has run) and are unpacked into d1 / d2; op streams
     // come down 2-bit from their own region ([cpos2][a letters byte per pair][packed2])
     const char* x2e = getenv("SEQALIB_XFER2");
     const bool xfer2 = packed && !(x2e && x2e[0] == '0');
+    // (score calls: the sequence half of the 2-bit transfers alone)
+    const bool xfer2_in = xfer2 || (notb && G == 1 && !small && !dc && !(x2e && x2e[0] == '0'));
     const uint64_t b_pk1 = al(t1 / 4 + 64);   // (seq2's landing zone follows seq1's)
+    const uint64_t b_pack = packed ? b_ops : xfer2_in ? b_pk1 + al((t2 + 3) / 4 + 64) : 0;
     const uint64_t b_cpos2 = xfer2 ? al(8ull * (npairs + 1)) + al(npairs) : 0, b_pack2 = xfer2 ? al(ops_total / 4 + npairs + 64) : 0;
     const uint64_t io_need = b_hdr + b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_lut + b_bits + b_cpos + b_pack + b_cpos2 + b_pack2;
     if (int rc = ensure_io(c, io_need)) return rc;
@@ -1642,7 +1694,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
     uint64_t* const dcpos2 = reinterpret_cast<uint64_t*>(p); p += b_cpos2;
     uint8_t* const dletters = reinterpret_cast<uint8_t*>(dcpos2 + (npairs + 1));   // per pair (ops_pack)
     uint8_t* const dpack2 = p;
-    if (xfer2 && b_pk1 + al((t2 + 3) / 4 + 64) > b_pack) return fail(c, SA_ERR_HIP, "internal: 2-bit landing zone");
+    if (xfer2_in && b_pk1 + al((t2 + 3) / 4 + 64) > b_pack) return fail(c, SA_ERR_HIP, "internal: 2-bit landing zone");
     // pinned staging (pageable copies were measured to stall 10-25 ms per call next to PyTorch),
     // laid out as the device I/O: in = [seq1][seq2][off1'][off2'], out = [results][ops], so that a
     // small call moves its inputs in one copy and its outputs in one copy
@@ -1672,7 +1724,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
     for (uint32_t g = 0; g < G; ++g) {
         const uint32_t p0 = cut[g], p1 = cut[g + 1];
         if (p1 == p0) continue;
-        const uint64_t ob = off1[p0] + off2[p0] + p0, on = off1[p1] + off2[p1] + p1 - ob;
+        const uint64_t ob = notb ? 0 : off1[p0] + off2[p0] + p0, on = notb ? 0 : off1[p1] + off2[p1] + p1 - ob;
         for (uint64_t x = 0; x < on || x == 0; x += kHostPiece) outp.push_back({g, ob + x, std::min(kHostPiece, on - x)});
     }
     while (c->host_ev.size() < (size_t)G + outp.size() + 1) {
@@ -1691,7 +1743,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
         const uint32_t p0 = cut[g], p1 = cut[g + 1], cnt = p1 - p0;
         if (!cnt) continue;
         const uint64_t a1 = off1[p0], a2 = off2[p0], n1 = off1[p1] - a1, n2 = off2[p1] - a2;
-        const uint64_t ob = a1 + a2 + p0, on = off1[p1] + off2[p1] + p1 - ob;   // the chunk's op bytes
+        const uint64_t ob = notb ? 0 : a1 + a2 + p0, on = notb ? 0 : off1[p1] + off2[p1] + p1 - ob;   // the chunk's op bytes
         uint32_t mm = 0, mn = 0;
         for (uint32_t q = 0; q <= cnt; ++q) {
             so1[p0 + g + q] = off1[p0 + q] - a1;
@@ -1711,7 +1763,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
         // one piece of a sequence buffer: 2-bit when every byte is A / C / G / T (packed into the
         // piece's own staging bytes, unpacked on the device), else the bytes
         auto put_piece = [&](uint8_t* dst, uint8_t* stg, const uint8_t* src, uint64_t k, uint8_t* land) -> int {
-            if (xfer2) {
+            if (xfer2_in) {
                 std::atomic<bool> ok{true};
                 par_for(k, CopyPool::kSlice, [&](uint64_t a, uint64_t b) {   // (slices: multiples of 4 bytes)
                     if (!dna2_pack(stg + a / 4, src + a, b - a)) ok.store(false, std::memory_order_relaxed);
@@ -1765,11 +1817,24 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
                 hs.up_src = shdr;
                 hs.up_bytes = small_up;
             }
+            // score calls of larger batches: more than 4 distinct symbols among the first bytes of
+            // either side prove the batch is no T16 candidate, so its int32 variant runs alone and no
+            // T16 records are provisioned (a batch of <= 4 is decided on the device, as ever)
+            bool many = false;
+            if (notb && n1 + n2 > kHostScanBytes) {
+                bool seen[256] = {};
+                int ns = 0;
+                for (uint64_t k = 0; k < std::min<uint64_t>(n1, kHostScanBytes / 2) && ns <= 4; ++k)
+                    if (!seen[seq1[a1 + k]]) { seen[seq1[a1 + k]] = true; ++ns; }
+                for (uint64_t k = 0; k < std::min<uint64_t>(n2, kHostScanBytes / 2) && ns <= 4; ++k)
+                    if (!seen[seq2[a2 + k]]) { seen[seq2[a2 + k]] = true; ++ns; }
+                many = ns > 4;
+            }
             int rc = run_device(c, algo, sc, d1 + a1, do1 + p0 + g, d2 + a2, do2 + p0 + g, cnt, mm, mn,
-                                use_lut ? dbits : nullptr, dres + p0, dops + ob, st, pipe, nullptr, nullptr,
-                                n1 + n2 <= kHostScanBytes ? &hs : nullptr);
+                                use_lut ? dbits : nullptr, dres + p0, notb ? nullptr : dops + ob, st, pipe, nullptr, nullptr,
+                                n1 + n2 <= kHostScanBytes ? &hs : nullptr, notb, many);
             if (rc) return rc;
-            if (pipe) done = c->s_tb;   // the chunk's last kernel (its traceback) ran there
+            if (pipe) done = c->s_tb;   // the chunk's last kernel (its traceback) ran there (score calls: it waits for the fill stream)
         }
         (void)on;
         if (packed) {   // (one chunk: p0 = 0, g = 0)
@@ -1801,7 +1866,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
         SA_HIP(c, hipMemcpyAsync(sres + p0, dres + p0, sizeof(sa_result) * cnt, hipMemcpyDeviceToHost, c->s_out));
         for (; next_out < outp.size() && outp[next_out].g == g; ++next_out) {
             const OutPiece& o = outp[next_out];
-            SA_HIP(c, hipMemcpyAsync(sops + o.ob, dops + o.ob, o.on, hipMemcpyDeviceToHost, c->s_out));
+            if (o.on) SA_HIP(c, hipMemcpyAsync(sops + o.ob, dops + o.ob, o.on, hipMemcpyDeviceToHost, c->s_out));
             SA_HIP(c, hipEventRecord(c->host_ev[G + next_out], c->s_out));
         }
     }
@@ -1871,7 +1936,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
         const auto t_o = std::chrono::steady_clock::now();
         if (k == 0 || outp[k - 1].g != o.g)
             memcpy(results + cut[o.g], sres + cut[o.g], sizeof(sa_result) * (cut[o.g + 1] - cut[o.g]));
-        par_copy(ops + o.ob, sops + o.ob, o.on);
+        if (o.on) par_copy(ops + o.ob, sops + o.ob, o.on);
         ms_out += since(t_o);
         if (cb && (k + 1 == outp.size() || outp[k + 1].g != o.g)) cb(cb_user, cut[o.g], cut[o.g + 1]);   // chunk landed
     }
@@ -1894,7 +1959,7 @@ int align_host(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, c
 // buffers are zero-filled placeholders of the right sizes.
 int align_host_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* off1, const uint64_t* off2,
                     uint32_t npairs, const uint32_t* bits, const uint64_t* bits_off, sa_result* results,
-                    uint8_t* ops, uint64_t ops_cap) {
+                    uint8_t* ops, uint64_t ops_cap, bool notb = false) {
     const uint64_t t1 = off1[npairs], t2 = off2[npairs], tw = bits_off[npairs];
     uint32_t max_m = 0, max_n = 0;
     for (uint32_t p = 0; p < npairs; ++p) {
@@ -1902,7 +1967,7 @@ int align_host_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* o
         max_m = (uint32_t)std::max<uint64_t>(max_m, off1[p + 1] - off1[p]);
         max_n = (uint32_t)std::max<uint64_t>(max_n, off2[p + 1] - off2[p]);
     }
-    const uint64_t ops_total = t1 + t2 + npairs;
+    const uint64_t ops_total = notb ? 0 : t1 + t2 + npairs;   // (score calls: no op region)
     if (ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer needs " + std::to_string(ops_total) + " bytes");
     if (!npairs) return SA_OK;
     auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
@@ -1938,12 +2003,12 @@ int align_host_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* o
         if (run(c->dc, c->ev_last_set ? c->ev_last : nullptr, sc, in, b, st, dres, dops, &e))
             return fail(c, SA_ERR_HIP, (algo == SA_HIRSCHBERG ? "hirschberg: " : "myers-miller: ") + e);
     } else {
-        int rc = run_device(c, algo, sc, dseq, do1, dseq, do2, npairs, max_m, max_n, nullptr, dres, dops, st, false,
-                            dbits, dbo);
+        int rc = run_device(c, algo, sc, dseq, do1, dseq, do2, npairs, max_m, max_n, nullptr, dres, notb ? nullptr : dops, st,
+                            false, dbits, dbo, nullptr, notb);
         if (rc) return rc;
     }
     SA_HIP(c, hipMemcpyAsync(results, dres, sizeof(sa_result) * npairs, hipMemcpyDeviceToHost, st));
-    SA_HIP(c, hipMemcpyAsync(ops, dops, ops_total, hipMemcpyDeviceToHost, st));
+    if (ops_total) SA_HIP(c, hipMemcpyAsync(ops, dops, ops_total, hipMemcpyDeviceToHost, st));
     SA_HIP(c, hipStreamSynchronize(st));
     return SA_OK;
 }
@@ -2070,55 +2135,69 @@ int sa_trim(sa_ctx* c) {
     return SA_OK;
 }
 
-int sa_align_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1,
-                   const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2, uint32_t npairs,
-                   const uint8_t* lut, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
-    return sa_align_batch_cb(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, ops_cap, 0, nullptr,
-                             nullptr);
+// ------------------------------------------------------------------------- batch calls
+// Every align entry point and its score counterpart (sa_score_batch*) share one body; notb marks
+// the score call: no ops buffer (ops NULL, ops_cap 0), no traceback (run_device, align_host).
+
+// The algorithm a score call runs: Hirschberg's score is NW's H[m][n]; Myers-Miller's is defined by
+// its own recursion, which a fill alone does not compute.
+static int score_algo(sa_ctx* c, int algo, int* out) {
+    if (algo == SA_MYERS_MILLER)
+        return fail(c, SA_ERR_UNSUPPORTED, "score calls do not support SA_MYERS_MILLER (its score is its own recursion's)");
+    *out = algo == SA_HIRSCHBERG ? SA_NW : algo;
+    return SA_OK;
 }
 
-int sa_align_batch_cb(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1,
-                      const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2, uint32_t npairs,
-                      const uint8_t* lut, sa_result* results, uint8_t* ops, uint64_t ops_cap, uint32_t chunks,
-                      sa_chunk_cb cb, void* cb_user) {
+// Context, scoring and algorithm checks of every batch call.
+static int batch_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, bool notb) {
     if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
-    int rc = validate_scoring(c, algo, sc);
+    if (int rc = validate_scoring(c, *algo, sc)) return rc;
+    return notb ? score_algo(c, *algo, algo) : SA_OK;
+}
+
+static int host_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                      const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
+                      sa_result* results, uint8_t* ops, uint64_t ops_cap, uint32_t chunks, sa_chunk_cb cb,
+                      void* cb_user, bool notb) {
+    int rc = batch_prologue(c, &algo, sc, notb);
     if (rc) return rc;
-    if (!off1 || !off2 || (npairs && (!results || !ops))) return fail(c, SA_ERR_ARG, "NULL buffer");
+    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
     if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
     if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
     SA_HIP(c, hipSetDevice(c->device));
     if ((rc = order_after_last(c, c->stream))) return rc;
 
     if (algo != SA_LOCAL_GOTOH)
-        return align_host(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, ops_cap, chunks, cb, cb_user);
+        return align_host(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, ops_cap, chunks, cb, cb_user,
+                          notb);
     // LocalGotoh: the size-hack pairs run as their own NW batch, so the whole range lands at the end
     rc = lg_hack_split(c, off1, off2, npairs, results, ops, ops_cap,
-                         [&](int a, const std::vector<uint32_t>& sel, const std::vector<uint64_t>& o1,
-                             const std::vector<uint64_t>& o2, sa_result* r, uint8_t* op, uint64_t cap) {
-                             if (sel.size() == npairs)
-                                 return align_host(c, a, sc, seq1, off1, seq2, off2, npairs, lut, r, op, cap);
-                             std::vector<uint8_t> s1, s2;
-                             s1.reserve(o1.back());
-                             s2.reserve(o2.back());
-                             for (uint32_t p : sel) {
-                                 s1.insert(s1.end(), seq1 + off1[p], seq1 + off1[p + 1]);
-                                 s2.insert(s2.end(), seq2 + off2[p], seq2 + off2[p + 1]);
-                             }
-                             return align_host(c, a, sc, s1.data(), o1.data(), s2.data(), o2.data(),
-                                               (uint32_t)sel.size(), lut, r, op, cap);
-                         });
+                       [&](int a, const std::vector<uint32_t>& sel, const std::vector<uint64_t>& o1,
+                           const std::vector<uint64_t>& o2, sa_result* r, uint8_t* op, uint64_t cap) {
+                           if (sel.size() == npairs)
+                               return align_host(c, a, sc, seq1, off1, seq2, off2, npairs, lut, r, op, cap, 0, nullptr,
+                                                 nullptr, notb);
+                           std::vector<uint8_t> s1, s2;
+                           s1.reserve(o1.back());
+                           s2.reserve(o2.back());
+                           for (uint32_t p : sel) {
+                               s1.insert(s1.end(), seq1 + off1[p], seq1 + off1[p + 1]);
+                               s2.insert(s2.end(), seq2 + off2[p], seq2 + off2[p + 1]);
+                           }
+                           return align_host(c, a, sc, s1.data(), o1.data(), s2.data(), o2.data(),
+                                             (uint32_t)sel.size(), lut, r, op, cap, 0, nullptr, nullptr, notb);
+                       },
+                       notb);
     if (rc == SA_OK && cb && npairs) cb(cb_user, 0, npairs);
     return rc;
 }
 
-int sa_align_batch_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* off1, const uint64_t* off2,
-                        uint32_t npairs, const uint32_t* bits, const uint64_t* bits_off, sa_result* results,
-                        uint8_t* ops, uint64_t ops_cap) {
-    if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
-    int rc = validate_scoring(c, algo, sc);
+static int host_batch_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* off1, const uint64_t* off2,
+                           uint32_t npairs, const uint32_t* bits, const uint64_t* bits_off, sa_result* results,
+                           uint8_t* ops, uint64_t ops_cap, bool notb) {
+    int rc = batch_prologue(c, &algo, sc, notb);
     if (rc) return rc;
-    if (!off1 || !off2 || !bits_off || (npairs && (!results || !ops))) return fail(c, SA_ERR_ARG, "NULL buffer");
+    if (!off1 || !off2 || !bits_off || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
     if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
     for (uint32_t p = 0; p < npairs; ++p) {
         const uint64_t m = off1[p + 1] - off1[p], n = off2[p + 1] - off2[p];
@@ -2129,12 +2208,12 @@ int sa_align_batch_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_
     SA_HIP(c, hipSetDevice(c->device));
     if ((rc = order_after_last(c, c->stream))) return rc;
     if (algo != SA_LOCAL_GOTOH)
-        return align_host_bits(c, algo, sc, off1, off2, npairs, bits, bits_off, results, ops, ops_cap);
+        return align_host_bits(c, algo, sc, off1, off2, npairs, bits, bits_off, results, ops, ops_cap, notb);
     return lg_hack_split(c, off1, off2, npairs, results, ops, ops_cap,
                          [&](int a, const std::vector<uint32_t>& sel, const std::vector<uint64_t>& o1,
                              const std::vector<uint64_t>& o2, sa_result* r, uint8_t* op, uint64_t cap) {
                              if (sel.size() == npairs)
-                                 return align_host_bits(c, a, sc, off1, off2, npairs, bits, bits_off, r, op, cap);
+                                 return align_host_bits(c, a, sc, off1, off2, npairs, bits, bits_off, r, op, cap, notb);
                              std::vector<uint32_t> b;
                              std::vector<uint64_t> bo(1, 0);
                              for (uint32_t p : sel) {
@@ -2142,18 +2221,17 @@ int sa_align_batch_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_
                                  bo.push_back(b.size());
                              }
                              return align_host_bits(c, a, sc, o1.data(), o2.data(), (uint32_t)sel.size(),
-                                                    b.data(), bo.data(), r, op, cap);
-                         });
+                                                    b.data(), bo.data(), r, op, cap, notb);
+                         },
+                         notb);
 }
 
-int sa_align_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1,
-                          const uint64_t* o1, const uint8_t* d2, const uint64_t* o2, uint32_t npairs,
-                          uint32_t max_m, uint32_t max_n, const uint8_t* d_lut, sa_result* d_res,
-                          uint8_t* d_ops, void* stream) {
-    if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
-    int rc = validate_scoring(c, algo, sc);
+static int device_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, const uint64_t* o1,
+                        const uint8_t* d2, const uint64_t* o2, uint32_t npairs, uint32_t max_m, uint32_t max_n,
+                        const uint8_t* d_lut, sa_result* d_res, uint8_t* d_ops, void* stream, bool notb) {
+    int rc = batch_prologue(c, &algo, sc, notb);
     if (rc) return rc;
-    if (!o1 || !o2 || (npairs && (!d_res || !d_ops))) return fail(c, SA_ERR_ARG, "NULL buffer");
+    if (!o1 || !o2 || (npairs && (!d_res || (!notb && !d_ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
     if (npairs == 0) return SA_OK;
     SA_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -2166,7 +2244,7 @@ int sa_align_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
         hipLaunchKernelGGL(lut_to_bits, dim3(8), dim3(256), 0, st, d_lut, bits);
         SA_HIP(c, hipGetLastError());
     }
-    if (algo == SA_HIRSCHBERG || algo == SA_MYERS_MILLER) {
+    if (algo == SA_HIRSCHBERG || algo == SA_MYERS_MILLER) {   // (align calls only: score_algo maps them away)
         std::string e;
         c->launches = 0;
         const auto run = algo == SA_HIRSCHBERG ? hirschberg_run : myersmiller_run;
@@ -2181,9 +2259,75 @@ int sa_align_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
         return mark_last(c, st);
     }
     const bool pipe = c->pipeline != 0;
-    rc = run_device(c, algo, sc, d1, o1, d2, o2, npairs, max_m, max_n, bits, d_res, d_ops, st, pipe);
+    rc = run_device(c, algo, sc, d1, o1, d2, o2, npairs, max_m, max_n, bits, d_res, d_ops, st, pipe, nullptr, nullptr,
+                    nullptr, notb);
     if (rc || pipe) return rc;
     return mark_last(c, st);
+}
+
+int sa_align_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1,
+                   const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2, uint32_t npairs,
+                   const uint8_t* lut, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    return host_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, ops_cap, 0, nullptr, nullptr, false);
+}
+
+int sa_align_batch_cb(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1,
+                      const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2, uint32_t npairs,
+                      const uint8_t* lut, sa_result* results, uint8_t* ops, uint64_t ops_cap, uint32_t chunks,
+                      sa_chunk_cb cb, void* cb_user) {
+    return host_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, ops, ops_cap, chunks, cb, cb_user, false);
+}
+
+int sa_score_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                   const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
+                   sa_result* results) {
+    return host_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, results, nullptr, 0, 0, nullptr, nullptr, true);
+}
+
+int sa_align_batch_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* off1, const uint64_t* off2,
+                        uint32_t npairs, const uint32_t* bits, const uint64_t* bits_off, sa_result* results,
+                        uint8_t* ops, uint64_t ops_cap) {
+    return host_batch_bits(c, algo, sc, off1, off2, npairs, bits, bits_off, results, ops, ops_cap, false);
+}
+
+int sa_score_batch_bits(sa_ctx* c, int algo, const sa_scoring* sc, const uint64_t* off1, const uint64_t* off2,
+                        uint32_t npairs, const uint32_t* bits, const uint64_t* bits_off, sa_result* results) {
+    return host_batch_bits(c, algo, sc, off1, off2, npairs, bits, bits_off, results, nullptr, 0, true);
+}
+
+int sa_align_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1,
+                          const uint64_t* o1, const uint8_t* d2, const uint64_t* o2, uint32_t npairs,
+                          uint32_t max_m, uint32_t max_n, const uint8_t* d_lut, sa_result* d_res,
+                          uint8_t* d_ops, void* stream) {
+    return device_batch(c, algo, sc, d1, o1, d2, o2, npairs, max_m, max_n, d_lut, d_res, d_ops, stream, false);
+}
+
+int sa_score_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, const uint64_t* o1,
+                          const uint8_t* d2, const uint64_t* o2, uint32_t npairs, uint32_t max_m, uint32_t max_n,
+                          const uint8_t* d_lut, sa_result* d_res, void* stream) {
+    return device_batch(c, algo, sc, d1, o1, d2, o2, npairs, max_m, max_n, d_lut, d_res, nullptr, stream, true);
+}
+
+int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,
+                        int* kernel, int* R, int* W, uint64_t* ws_bytes_per_pair) {
+    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(nullptr, SA_ERR_ARG, "unknown algorithm");
+    if (!sc) return fail(nullptr, SA_ERR_ARG, "scoring is NULL");
+    int rc = score_algo(nullptr, algo, &algo);
+    if (rc) return rc;
+    // the variants sa_score_batch enqueues: a batch of more than 4 symbols is known as such on the
+    // host (align_host), so T16 is no candidate and nothing is provisioned for it
+    const bool cand = nsym <= 4 && t16_candidate(algo, sc, max_m, max_n, npairs).ok;
+    Variant vars[3];
+    bool has_fb = false;
+    const int nv = build_variants(algo, max_m, max_n, npairs, cand, vars, &has_fb, 0, true);
+    const Variant& v = vars[0];
+    if (kernel) *kernel = v.kernel;
+    if (R) *R = v.pl.R;
+    if (W) *W = v.pl.split ? 0 : v.pl.W;
+    uint64_t ws = 0;
+    for (int k = 0; k < nv + (has_fb ? 1 : 0); ++k) ws = std::max(ws, vars[k].slot_bytes);
+    if (ws_bytes_per_pair) *ws_bytes_per_pair = ws;
+    return SA_OK;
 }
 
 int sa_set_pipeline(sa_ctx* c, int enable) {
@@ -2223,6 +2367,7 @@ int sa_last_timings(sa_ctx* c, float* fill_ms, float* tb_ms, int* launches) {
         f += a;
         t += b;
     }
+    if (c->tb_kernels == 0) t = 0.f;   // no kernel behind the fills (a score call): not the gap between two records
     if (fill_ms) *fill_ms = f;
     if (tb_ms) *tb_ms = t;
     if (launches) *launches = c->launches;

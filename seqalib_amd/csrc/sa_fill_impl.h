@@ -115,6 +115,15 @@ __device__ __forceinline__ bool match_bit(const uint32_t* s_lut, int a, int b) {
 // which need > 128 VGPRs per lane.
 template <int R, bool WIDE = false>
 constexpr int fill_max_threads() { return (R >= 32 || (WIDE && R >= 16)) ? 256 : 1024; }
+// The record-free int32 kernels (NOREC) at R = 16, and at R = 8 with match bitmaps (R more
+// registers for the rows' bit windows): 8 waves.  Under the 128 VGPRs of a 16-wave workgroup the
+// local-mode cells (a, H, best score and column per row) spill 20 - 256 bytes per lane, as the
+// recording kernels do (profiles/score_fill_resources.txt); make_variant (sa_api.hip) caps W.
+constexpr int kNorecWideThreads = 512;
+template <int R, bool WIDE, bool NOREC, int MM>
+constexpr int fill_kernel_threads() {
+    return (NOREC && (R >= 16 || (R >= 8 && MM == kMatchBits))) ? kNorecWideThreads : fill_max_threads<R, WIDE>();
+}
 
 // Bounded wait of a SPLIT band for its producer: FillParams::wait_ticks (kSplitWaitTicksDefault,
 // 0.2 s; SEQALIB_SPLIT_WAIT_TICKS overrides it for tests).  After one expiry the workgroup stops
@@ -226,7 +235,12 @@ __device__ __forceinline__ uint32_t bu_fold_parts(const unsigned long long __att
 // lane-step).  With the per-chunk snapshots every (lane, chunk) block of R x 32 cells can be
 // recomputed exactly from its left column (snapshot), its top row (edge stream of the lane above,
 // or the band's top row) and its corner, which sa_traceback_so.hip does along the path.
-template <int ALG, int R, int MM, bool ALLOW, bool KEYED, bool T16, bool CMAX, bool SPLIT, bool SO = false>
+// NOREC (the score calls, sa_score_batch*; int32 cells only): the cell pushes no traceback flags and
+// the chunk loop builds and stores no record packets -- P.dirs is never touched and a pair's
+// workspace is its row buffer alone.  Everything else (hand-offs, the running maximum and its end
+// cell, the results) is the recording kernel's.
+template <int ALG, int R, int MM, bool ALLOW, bool KEYED, bool T16, bool CMAX, bool SPLIT, bool SO = false,
+          bool NOREC = false>
 // (Asking the headline kernel for 4 waves per SIMD -- 128 VGPRs, 8 spills outside the step loops
 // -- measured 29.6 ms per fill against 29.4 at its natural 3 waves: not taken.)
 __device__ __forceinline__ void fill_body(const FillParams& P) {
@@ -273,6 +287,7 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
     constexpr bool SOMAX = SO && ALG == SA_SW;
     constexpr int CSH = SO ? 0 : (AFF ? 3 : 2);   // CMAX: chunk maxima are H << CSH
     static_assert(!CMAX || (T16 && LOCAL && R % 2 == 0), "CMAX: T16 Smith-Waterman / LocalGotoh");
+    static_assert(!NOREC || (!T16 && !CMAX && !SO), "NOREC: the int32 cell");
 
     // Dynamic LDS (sizes from lds_layout(), host and device agree):
     //   [match bits: 2048 words, LUT only][hand-off rings: W x kRing x (1|2) ints][Seq2 bytes, staged]
@@ -677,7 +692,7 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
         // T16: the v_alignbit pushes shift every bit a word held out of it, and a lane-step outside
         // the matrix only fills its own (never read) record bytes -- except a narrow record of
         // kStepAny, ORed into its packet word unshifted when the lane-step is outside: zeroed
-        if constexpr (!T16 || (RB < 32 && !ACC) || (RB > 32 && RB % 32 != 0)) {
+        if constexpr (!NOREC && (!T16 || (RB < 32 && !ACC) || (RB > 32 && RB % 32 != 0))) {
 #pragma unroll
             for (int e = 0; e < RW; ++e) rec[e] = 0;
         }
@@ -974,17 +989,19 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
                 int D;
                 if constexpr (ALLOW) D = hd + (v ? MA : MI);
                 else D = v ? hd + MA : INT_MIN;
-                if constexpr (BPC > FBITS) rw <<= BPC - FBITS;   // record padding (R <= 2)
+                if constexpr (BPC > FBITS && !NOREC) rw <<= BPC - FBITS;   // record padding (R <= 2)
                 if constexpr (!AFF) {
                     const int U = hu + G;
                     const int L = Hp[r] + G;
                     int H = imax(imax(D, U), L);
                     if constexpr (LOCAL) H = imax(H, 0);
-                    rw = push_eq(rw, H, D);   // fD
-                    // BITS: the second bit is the match bit when fD is set (the traceback's diag
-                    // move then needs no symbols), fU otherwise
-                    if constexpr (BITS) rw = push_bit(rw, H == D ? v : H == U);
-                    else rw = push_eq(rw, H, U);   // fU
+                    if constexpr (!NOREC) {
+                        rw = push_eq(rw, H, D);   // fD
+                        // BITS: the second bit is the match bit when fD is set (the traceback's diag
+                        // move then needs no symbols), fU otherwise
+                        if constexpr (BITS) rw = push_bit(rw, H == D ? v : H == U);
+                        else rw = push_eq(rw, H, U);   // fU
+                    }
                     Hc = H;
                 } else {
                     const int XE = xu + GE;
@@ -993,11 +1010,13 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
                     const int Y = imax(Hp[r] + GOE, YE);
                     int M = imax(imax(D, X), Y);
                     if constexpr (LOCAL) M = imax(M, 0);
-                    rw = push_eq(rw, M, D);   // fD
-                    if constexpr (BITS) rw = push_bit(rw, M == D ? v : M == X);   // fX, or v under fD
-                    else rw = push_eq(rw, M, X);   // fX
-                    rw = push_eq(rw, X, XE);  // fXe: Ix extends
-                    rw = push_eq(rw, Y, YE);  // fYe: Iy extends
+                    if constexpr (!NOREC) {
+                        rw = push_eq(rw, M, D);   // fD
+                        if constexpr (BITS) rw = push_bit(rw, M == D ? v : M == X);   // fX, or v under fD
+                        else rw = push_eq(rw, M, X);   // fX
+                        rw = push_eq(rw, X, XE);  // fXe: Ix extends
+                        rw = push_eq(rw, Y, YE);  // fYe: Iy extends
+                    }
                     Yp[r] = Y;
                     xu = X;
                     Hc = M;
@@ -1115,6 +1134,7 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
     auto run_chunk = [&](auto steady, int band, int kC, int bch, int bcx, int symc, int& acc_h,
                          int& acc_x) {
         uint8_t* const dband = dslot + (uint64_t)band * P.band_stride;
+        (void)dband;
 #pragma unroll 1
         for (int q0 = 0; q0 < kChunk; q0 += SPP) {
             uint32_t pk[4 * PPS];
@@ -1162,7 +1182,9 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
                         case 2: step(steady, q, kC + q, vh, vx, vs, rec, std::integral_constant<int, 2>{}); break;
                         default: step(steady, q, kC + q, vh, vx, vs, rec, std::integral_constant<int, 3>{}); break;
                     }
-                    if constexpr (BPS >= 4) {
+                    if constexpr (NOREC) {
+                        // (no record: the step left rec untouched)
+                    } else if constexpr (BPS >= 4) {
 #pragma unroll
                         for (int e = 0; e < RW; ++e) pk[g * RW + e] = rec[e];
                     } else {
@@ -1181,12 +1203,14 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
                     }
                 }
             }
-            const uint64_t pkt0 = (uint64_t)((kC + q0) / SPP) * PPS;
+            if constexpr (!NOREC) {
+                const uint64_t pkt0 = (uint64_t)((kC + q0) / SPP) * PPS;
 #pragma unroll
-            for (int pp = 0; pp < PPS; ++pp) {
-                u32x4* dst = reinterpret_cast<u32x4*>(dband + ((pkt0 + pp) * kWave + lane) * 16);
-                const u32x4 v4 = {pk[pp * 4 + 0], pk[pp * 4 + 1], pk[pp * 4 + 2], pk[pp * 4 + 3]};
-                __builtin_nontemporal_store(v4, dst);
+                for (int pp = 0; pp < PPS; ++pp) {
+                    u32x4* dst = reinterpret_cast<u32x4*>(dband + ((pkt0 + pp) * kWave + lane) * 16);
+                    const u32x4 v4 = {pk[pp * 4 + 0], pk[pp * 4 + 1], pk[pp * 4 + 2], pk[pp * 4 + 3]};
+                    __builtin_nontemporal_store(v4, dst);
+                }
             }
         }
         // lane q < kChunk: the band's last row at column kC + q - 63
@@ -1639,9 +1663,10 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
     }
 }
 
-template <int ALG, int R, int MM, bool ALLOW, bool KEYED, bool T16, bool CMAX, bool SPLIT, bool SO = false>
-__global__ __launch_bounds__((fill_max_threads<R, (T16 && ALG >= SA_LOCAL_GOTOH)>())) void fill_kernel(FillParams P) {
-    fill_body<ALG, R, MM, ALLOW, KEYED, T16, CMAX, SPLIT, SO>(P);
+template <int ALG, int R, int MM, bool ALLOW, bool KEYED, bool T16, bool CMAX, bool SPLIT, bool SO = false,
+          bool NOREC = false>
+__global__ __launch_bounds__((fill_kernel_threads<R, (T16 && ALG >= SA_LOCAL_GOTOH), NOREC, MM>())) void fill_kernel(FillParams P) {
+    fill_body<ALG, R, MM, ALLOW, KEYED, T16, CMAX, SPLIT, SO, NOREC>(P);
 }
 // The score-only kernel (one wave per workgroup): 4 waves per SIMD.  Its cell needs no record
 // registers, and the fourth wave hides the cell's dependent 16-bit chain (tools/microbench_so.hip:
@@ -1651,6 +1676,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     constexpr bool LOCAL = ALG == SA_SW || ALG == SA_LOCAL_GOTOH;
     fill_body<ALG, R, kMatchEq, true, LOCAL, true, LOCAL, false, true>(P);
 }
+
+template <int ALG, bool NOREC>
+hipError_t launch_fill_int32(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream);
 
 template <int ALG>
 hipError_t launch_fill_alg(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream) {
@@ -1745,19 +1773,36 @@ hipError_t launch_fill_alg(const FillVariant& v, const FillParams& p, uint32_t g
             return hipErrorInvalidValue;
         }
     }
-    if (v.t16 || v.cmax || v.so) return hipErrorInvalidValue;
+    if (v.t16 || v.cmax || v.so || v.norec) return hipErrorInvalidValue;
+    return launch_fill_int32<ALG, false>(v, p, grid, stream);
+}
+
+// The int32 kernels of one algorithm; NOREC: their record-free twins (sa_fill_*_score.hip).
+template <int ALG, bool NOREC>
+hipError_t launch_fill_int32(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream) {
+    constexpr bool LOCAL = (ALG == SA_SW || ALG == SA_LOCAL_GOTOH);
+    const int R = v.R;
+    if (v.t16 || v.cmax || v.so || v.norec != NOREC) return hipErrorInvalidValue;
+    const bool lut = v.bits ? false : v.lut, allow = v.allow;
+    const bool keyed = LOCAL && v.keyed;
+    const dim3 block(kWave * (v.split ? 3 : p.waves));
+    if (NOREC && R >= 8 && (int)block.x > kNorecWideThreads) return hipErrorInvalidConfiguration;
+    const size_t lds = lds_layout(lut, is_affine(ALG), p.waves, p.stage_seq2 ? p.max_n : 0).total;
+    if (lds > kMaxLds) return hipErrorInvalidConfiguration;
+    const bool split = v.split;
+    if (split && (p.waves != 1 || (R != 1 && R != 2 && R != 4 && R != 8))) return hipErrorInvalidConfiguration;
     const int mm = v.bits ? kMatchBits : lut ? kMatchLut : kMatchEq;
 #define SA_LAUNCH(RR, MMV, AA, KK)                                                             \
     if (R == RR && mm == MMV && allow == AA && keyed == KK) {                                  \
         if (split) {                                                                           \
             if constexpr (RR <= 8) {                                                           \
-                hipLaunchKernelGGL((fill_kernel<ALG, RR, MMV, AA, KK, false, false, true>), dim3(grid), block, lds, \
+                hipLaunchKernelGGL((fill_kernel<ALG, RR, MMV, AA, KK, false, false, true, false, NOREC>), dim3(grid), block, lds, \
                                    stream, p);                                                 \
                 return hipGetLastError();                                                      \
             }                                                                                  \
             return hipErrorInvalidConfiguration;                                               \
         }                                                                                      \
-        hipLaunchKernelGGL((fill_kernel<ALG, RR, MMV, AA, KK, false, false, false>), dim3(grid), block, lds, stream, p); \
+        hipLaunchKernelGGL((fill_kernel<ALG, RR, MMV, AA, KK, false, false, false, false, NOREC>), dim3(grid), block, lds, stream, p); \
         return hipGetLastError();                                                              \
     }
 #define SA_LAUNCH_K(RR, MMV, AA) \
@@ -1777,7 +1822,7 @@ hipError_t launch_fill_alg(const FillVariant& v, const FillParams& p, uint32_t g
     // R = 1, 2: the few-pairs (SPLIT) plans only
 #define SA_LAUNCH_S(RR, MMV, AA, KK)                                                            \
     if (split && R == RR && mm == MMV && allow == AA && keyed == KK) {                          \
-        hipLaunchKernelGGL((fill_kernel<ALG, RR, MMV, AA, KK, false, false, true>), dim3(grid), block, lds, stream, p); \
+        hipLaunchKernelGGL((fill_kernel<ALG, RR, MMV, AA, KK, false, false, true, false, NOREC>), dim3(grid), block, lds, stream, p); \
         return hipGetLastError();                                                               \
     }
 #define SA_LAUNCH_SK(RR, MMV, AA) \

@@ -227,12 +227,23 @@ struct FillVariant {
     bool bits = false;   // kMatchBits (then lut is ignored)
     bool so = false;     // score-only T16 SW chunk-max fill (edge stream instead of records)
     bool so2 = false;    // score-only SW with two pairs per wave (sa_fill_so2.hip)
+    bool norec = false;  // the score calls' int32 fill: no flags, no record stores (fill_body NOREC)
 };
 hipError_t launch_fill(int algo, const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream);
 hipError_t launch_fill_sw(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
 hipError_t launch_fill_nw(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
 hipError_t launch_fill_lg(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
 hipError_t launch_fill_gg(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+// The record-free int32 fills (FillVariant::norec), one translation unit each (sa_fill_*_score.hip).
+hipError_t launch_fill_sw_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_nw_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_lg_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_gg_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_score(int algo, const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream);
+// The last kernel of a score call (sa_score_batch*): no walk follows the fills, so this clears what
+// a walk would have -- the internal flags (kFlagRetry / kFlagRerun / kFlagRedo) and the end-cell
+// replay's `reserved` word -- and writes the score contract's start = (-1, -1), nops = 0.
+hipError_t launch_score_finish(sa_result* res, uint32_t pair_base, uint32_t count, hipStream_t s);
 // Score-only SW band units with two pairs per wave (sa_fill_so2.hip), R in {16, 32}: grid =
 // ceil(count / 2) x bands x part_segs units.
 hipError_t launch_fill_so2(int algo, int R, const FillParams& p, uint32_t grid, hipStream_t s);
@@ -344,5 +355,7 @@ struct TinyParams {
     int32_t gap, match, mismatch, gap_open, gap_extend;
     int allow;
 };
-hipError_t launch_tiny(int algo, bool lut, int max_m, const TinyParams& p, hipStream_t stream);
+// score: the kernel stops after the fill (no flag stores to LDS, no walk, no ops; the results follow
+// the score contract, include/seqalib_hip.h sa_score_batch)
+hipError_t launch_tiny(int algo, bool lut, int max_m, const TinyParams& p, hipStream_t stream, bool score = false);
 }  // namespace sa

@@ -110,4 +110,37 @@ int sa_multi_align_batch(sa_multi* g, int algo, const sa_scoring* scoring, const
     return SA_OK;
 }
 
+// sa_score_batch over the handle's contexts: the same ranges, each writing its results in place
+// (no op buffers anywhere).
+int sa_multi_score_batch(sa_multi* g, int algo, const sa_scoring* scoring, const uint8_t* seq1,
+                         const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2, uint32_t npairs,
+                         const uint8_t* lut, sa_result* results) {
+    if (!g) return mfail(nullptr, SA_ERR_ARG, "handle is NULL");
+    if (!off1 || !off2 || (npairs && !results)) return mfail(g, SA_ERR_ARG, "NULL buffer");
+    if (off1[0] != 0 || off2[0] != 0) return mfail(g, SA_ERR_ARG, "offsets must start at 0");
+    for (uint32_t p = 0; p < npairs; ++p)
+        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return mfail(g, SA_ERR_ARG, "offsets must be non-decreasing");
+    const size_t G = g->ctx.size();
+    const std::vector<uint32_t> cut = split_by_cells(off1, off2, npairs, G);
+    std::vector<int> rc(G, SA_OK);
+    auto work = [&](size_t d) {
+        const uint32_t s = cut[d], e = cut[d + 1];
+        if (e <= s) return;
+        std::vector<uint64_t> o1(e - s + 1), o2(e - s + 1);
+        for (uint32_t p = s; p <= e; ++p) {
+            o1[p - s] = off1[p] - off1[s];
+            o2[p - s] = off2[p] - off2[s];
+        }
+        rc[d] = sa_score_batch(g->ctx[d], algo, scoring, seq1 ? seq1 + off1[s] : nullptr, o1.data(),
+                               seq2 ? seq2 + off2[s] : nullptr, o2.data(), e - s, lut, results + s);
+    };
+    std::vector<std::thread> th;
+    for (size_t d = 1; d < G; ++d) th.emplace_back(work, d);
+    work(0);
+    for (auto& t : th) t.join();
+    for (size_t d = 0; d < G; ++d)
+        if (rc[d] != SA_OK) return mfail(g, rc[d], "context " + std::to_string(d) + ": " + sa_last_error(g->ctx[d]));
+    return SA_OK;
+}
+
 }  // extern "C"

@@ -21,15 +21,17 @@
 namespace sa {
 
 // one lane owns R consecutive rows; lane t computes column s - t at step s (as the fill)
-template <int ALG, int R, bool LUT>
+// SCORE (the score calls, sa_score_batch): the kernel stops after the fill -- no flag array in LDS,
+// no flag stores, no walk, no ops; the result follows the score contract (start = (-1, -1), nops = 0).
+template <int ALG, int R, bool LUT, bool SCORE = false>
 __global__ __launch_bounds__(64) void tiny_kernel(TinyParams P) {
     constexpr bool AFF = ALG >= SA_LOCAL_GOTOH;
     constexpr bool LOCAL = ALG == SA_SW || ALG == SA_LOCAL_GOTOH;
     constexpr int kNeg = -10000;   // the reference's Ix / Iy border (SALocalGotoh.h:77-90)
-    __shared__ uint8_t s_flag[kTinyCells];     // cell (i, j), 1-based: (i - 1) * n + j - 1
+    __shared__ uint8_t s_flag[SCORE ? 1 : kTinyCells];     // cell (i, j), 1-based: (i - 1) * n + j - 1
     __shared__ uint8_t s_a[kTinyM], s_b[kTinyN];
     __shared__ uint32_t s_lut[LUT ? 2048 : 1];
-    __shared__ uint8_t s_ops[kTinyM + kTinyN + 1];
+    __shared__ uint8_t s_ops[SCORE ? 1 : kTinyM + kTinyN + 1];
     __shared__ int s_score;
     const int lane = threadIdx.x;
     const uint32_t p = blockIdx.x;
@@ -100,7 +102,8 @@ __global__ __launch_bounds__(64) void tiny_kernel(TinyParams P) {
                             Yp[r] = Y;
                             xu = X;
                         }
-                        s_flag[(row0 + r) * n + j] = (uint8_t)f;
+                        if constexpr (!SCORE) s_flag[(row0 + r) * n + j] = (uint8_t)f;
+                        (void)f;
                         hd = Hp[r];
                         Hp[r] = Hn;
                         hu = Hn;
@@ -135,6 +138,25 @@ __global__ __launch_bounds__(64) void tiny_kernel(TinyParams P) {
     }
     __syncthreads();   // the flags and s_score
 
+    if constexpr (SCORE) {
+        if (lane == 0) {
+            sa_result res = {};
+            if constexpr (LOCAL) {
+                const bool cells = m > 0 && n > 0;
+                res.score = cells ? best_h : (ALG == SA_SW ? INT_MIN : 0);
+                res.end_i = cells ? best_i : 0;
+                res.end_j = cells ? best_j : 0;
+            } else {
+                res.score = (m > 0 && n > 0) ? s_score : border(m > n ? m : n);
+                res.end_i = m;
+                res.end_j = n;
+            }
+            res.start_i = -1;
+            res.start_j = -1;
+            P.res[p] = res;
+        }
+        return;
+    }
     // ---- traceback (one lane), as sa_traceback.hip walks the int32 records
     sa_result res = {};
     if (lane == 0) {
@@ -221,12 +243,20 @@ __global__ __launch_bounds__(64) void tiny_kernel(TinyParams P) {
     if (lane == 0) P.res[p] = res;
 }
 
-hipError_t launch_tiny(int algo, bool lut, int max_m, const TinyParams& p, hipStream_t stream) {
+hipError_t launch_tiny(int algo, bool lut, int max_m, const TinyParams& p, hipStream_t stream, bool score) {
     const dim3 grid(p.npairs), block(64);
     const bool r4 = max_m > kWave;   // R = 1 row per lane up to 64 rows, else 4
 #define SA_TINY(A)                                                                                            \
     case A:                                                                                                   \
-        if (lut) {                                                                                            \
+        if (score) {                                                                                          \
+            if (lut) {                                                                                        \
+                if (r4) hipLaunchKernelGGL((tiny_kernel<A, 4, true, true>), grid, block, 0, stream, p);         \
+                else hipLaunchKernelGGL((tiny_kernel<A, 1, true, true>), grid, block, 0, stream, p);            \
+            } else {                                                                                          \
+                if (r4) hipLaunchKernelGGL((tiny_kernel<A, 4, false, true>), grid, block, 0, stream, p);        \
+                else hipLaunchKernelGGL((tiny_kernel<A, 1, false, true>), grid, block, 0, stream, p);           \
+            }                                                                                                 \
+        } else if (lut) {                                                                                          \
             if (r4) hipLaunchKernelGGL((tiny_kernel<A, 4, true>), grid, block, 0, stream, p);                   \
             else hipLaunchKernelGGL((tiny_kernel<A, 1, true>), grid, block, 0, stream, p);                      \
         } else {                                                                                              \

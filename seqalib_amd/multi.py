@@ -88,6 +88,27 @@ class MultiEngine:
             raise RuntimeError(f"sa_multi_align_batch: {self.L.sa_multi_last_error(self.h).decode()}")
         return res[:npairs], ops
 
+    def score_packed(self, algo: int, scoring: ScoringSystem, s1, o1, s2, o2, lut: Optional[np.ndarray] = None):
+        """sa_multi_score_batch: the results of Engine.score_packed, computed on the handle's devices."""
+        import ctypes as C
+        from . import _ptr
+        npairs = len(o1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        o1 = np.ascontiguousarray(o1, dtype=np.uint64)
+        o2 = np.ascontiguousarray(o2, dtype=np.uint64)
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_multi_score_batch(self.h, algo, C.byref(sc), _ptr(s1), _ptr(o1), _ptr(s2), _ptr(o2), npairs,
+                                         lut_p or None, _ptr(res))
+        if rc:
+            raise RuntimeError(f"sa_multi_score_batch: {self.L.sa_multi_last_error(self.h).decode()}")
+        return res[:npairs]
+
     def close(self):
         if self.h:
             self.L.sa_multi_destroy(self.h)
@@ -123,3 +144,14 @@ def align_multi_gpu(algo: int, scoring: ScoringSystem, s1: np.ndarray, o1: np.nd
     if eng is None:
         eng = _multi_cache[key] = MultiEngine(devices)
     return eng.align_packed(algo, scoring, s1, o1, s2, o2, lut)
+
+
+def score_multi_gpu(algo: int, scoring: ScoringSystem, s1: np.ndarray, o1: np.ndarray, s2: np.ndarray,
+                    o2: np.ndarray, devices: Sequence[int], lut: Optional[np.ndarray] = None):
+    """Score a batch on several GPUs of this node (no traceback): the results array of a single-GPU
+    sa_score_batch."""
+    key = tuple(devices)
+    eng = _multi_cache.get(key)
+    if eng is None:
+        eng = _multi_cache[key] = MultiEngine(devices)
+    return eng.score_packed(algo, scoring, s1, o1, s2, o2, lut)
