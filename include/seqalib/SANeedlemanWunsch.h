@@ -21,24 +21,45 @@ public:
     }
 
     std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
-        std::vector<sa_result> res;
-        auto out = seqalib::detail::run<SA_NW, NeedlemanWunschSA, ContainerType, Ty, Blank>(*this, pairs, res);
-        if (!res.empty()) LastScore = res.back().score;
-        return out;
+        return alignBatch(pairs, seqalib::detail::kNoBand);
+    }
+    // Extension: banded NW (sa_align_batch_banded): only the cells within `band` diagonals of each
+    // pair's corner-to-corner corridor, O((m + n) * band) work and memory per pair.  With
+    // band >= max(m, n) the result is getAlignments(pairs).  Byte-sized symbols, or batches of at most
+    // 256 distinct symbols; others throw std::runtime_error.
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band) {
+        return alignBatch(pairs, seqalib::detail::band_of(band));
     }
 
     // Extension: the getScore() of every pair in one GPU pass with no traceback (no AlignedSequence is
     // built, no op buffer allocated); getScore() afterwards returns the last pair's.
     std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        return scoreBatch(pairs, seqalib::detail::kNoBand);
+    }
+    // Extension: the banded scores (sa_score_batch_banded), as getAlignments(pairs, band).
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band) {
+        return scoreBatch(pairs, seqalib::detail::band_of(band));
+    }
+
+    // Extension: H[m][n] of the last alignment.
+    ScoreSystemType getScore() const { return LastScore; }
+
+private:
+    std::vector<AlignedSequence<Ty, Blank>> alignBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                       long long band) {
         std::vector<sa_result> res;
-        seqalib::detail::run_scores<SA_NW, NeedlemanWunschSA, ContainerType, Ty>(*this, pairs, res);
+        auto out = seqalib::detail::run<SA_NW, NeedlemanWunschSA, ContainerType, Ty, Blank>(*this, pairs, res, band);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+    std::vector<ScoreSystemType> scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, long long band) {
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_NW, NeedlemanWunschSA, ContainerType, Ty>(*this, pairs, res, band);
         std::vector<ScoreSystemType> out;
         out.reserve(res.size());
         for (auto& r : res) out.push_back(r.score);
         if (!res.empty()) LastScore = res.back().score;
         return out;
     }
-
-    // Extension: H[m][n] of the last alignment.
-    ScoreSystemType getScore() const { return LastScore; }
 };

@@ -33,12 +33,36 @@ public:
 
     // Batch extension: one GPU pass over many pairs (configs 3/5 of BASELINE.json).
     std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs) {
+        return alignBatch(pairs, seqalib::detail::kNoBand);
+    }
+    // Extension: banded SW (sa_align_batch_banded): only the cells within `band` diagonals of each
+    // pair's corner-to-corner corridor; the end cell is the last in-band maximum.  With
+    // band >= max(m, n) the result is getAlignments(pairs).  Byte-sized symbols, or batches of at most
+    // 256 distinct symbols; others throw std::runtime_error.  getScores / getEndCells likewise.
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band) {
+        return alignBatch(pairs, seqalib::detail::band_of(band));
+    }
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band) {
+        std::vector<std::pair<size_t, size_t>> cells;
+        return scoreBatch(pairs, cells, seqalib::detail::band_of(band));
+    }
+    std::vector<std::pair<size_t, size_t>> getEndCells(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                       size_t band) {
+        std::vector<std::pair<size_t, size_t>> cells;
+        scoreBatch(pairs, cells, seqalib::detail::band_of(band));
+        return cells;
+    }
+
+private:
+    std::vector<AlignedSequence<Ty, Blank>> alignBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                       long long band) {
         std::vector<std::pair<ContainerType*, ContainerType*>> work;
         for (auto& p : pairs)
             if (p.first->size() && p.second->size()) work.push_back(p);
         std::vector<sa_result> res;
         std::vector<AlignedSequence<Ty, Blank>> done;
-        if (!work.empty()) done = seqalib::detail::run<SA_SW, SmithWatermanSA, ContainerType, Ty, Blank>(*this, work, res);
+        if (!work.empty()) done = seqalib::detail::run<SA_SW, SmithWatermanSA, ContainerType, Ty, Blank>(*this, work, res, band);
         std::vector<AlignedSequence<Ty, Blank>> out;
         out.reserve(pairs.size());
         size_t k = 0;
@@ -55,6 +79,7 @@ public:
         return out;
     }
 
+public:
     // Extensions: scores / end cells of every pair in one GPU pass with no traceback (no
     // AlignedSequence is built, no op buffer allocated).  The members move as in getAlignments: a
     // pair with an empty side scores INT_MIN and keeps the end cell of the pair before it.
@@ -74,12 +99,13 @@ public:
 
 private:
     std::vector<ScoreSystemType> scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                                            std::vector<std::pair<size_t, size_t>>& cells) {
+                                            std::vector<std::pair<size_t, size_t>>& cells,
+                                            long long band = seqalib::detail::kNoBand) {
         std::vector<std::pair<ContainerType*, ContainerType*>> work;
         for (auto& p : pairs)
             if (p.first->size() && p.second->size()) work.push_back(p);
         std::vector<sa_result> res;
-        seqalib::detail::run_scores<SA_SW, SmithWatermanSA, ContainerType, Ty>(*this, work, res);
+        seqalib::detail::run_scores<SA_SW, SmithWatermanSA, ContainerType, Ty>(*this, work, res, band);
         std::vector<ScoreSystemType> out;
         out.reserve(pairs.size());
         cells.clear();

@@ -185,7 +185,7 @@ constexpr size_t kChunkPairs = SIZE_MAX;
 // callbacks hand each landed range to a builder thread (which fans out over the host threads).
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty, Ty Blank>
 std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                                            std::vector<sa_result>& res) {
+                                            std::vector<sa_result>& res, long long band = kNoBand) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
@@ -211,9 +211,9 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
     PhaseTimer tm;
     size_t cp = kChunkPairs;
     if (const char* e = std::getenv("SEQALIB_LIST_CHUNK_PAIRS")) cp = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
-    const size_t G = cp <= P / 2 ? (P + cp - 1) / cp : 1;
+    const size_t G = band == kNoBand && cp <= P / 2 ? (P + cp - 1) / cp : 1;   // (a banded call is one range)
     if (G == 1) {
-        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off);
+        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band);
         build_range(0, P);
         tm.lap("AlignedSequence lists");
         return out;
@@ -275,12 +275,12 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
 // buffers) over the batch; res[p] holds pair p's score and end cell.
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty>
 void run_scores(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                std::vector<sa_result>& res) {
+                std::vector<sa_result>& res, long long band = kNoBand) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
     res.clear();
-    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res);
+    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band);
 }
 
 }  // namespace detail

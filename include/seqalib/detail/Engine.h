@@ -382,6 +382,24 @@ void pack_batch(PackedBatch<Ty>& pk, const std::vector<std::pair<ContainerType*,
 // chunks > 1: the GPU call runs in that many pair ranges (sa_align_batch_cb) and on_chunk(p0, p1)
 // is called, on this thread, as soon as a range's results and op streams are in res / ops (the
 // other paths report the whole batch once at the end).
+// band >= 0: the banded call of that half-width (sa_align_batch_banded / sa_score_batch_banded), on
+// this thread's context; it takes byte symbols or a symbol table, not per-pair bitmaps.
+constexpr long long kNoBand = -1;
+constexpr size_t kBandedMaxSymbols = 256;
+inline uint32_t band_arg(long long band) {
+    if (band > 0xffffffffLL) throw std::runtime_error("seqalib: band does not fit 32 bits");
+    return (uint32_t)band;
+}
+// A caller's size_t half-width as the band argument of run() / run_scores(): never kNoBand.
+inline long long band_of(size_t band) {
+    if (band > 0xffffffffull) throw std::runtime_error("seqalib: band does not fit 32 bits");
+    return (long long)band;
+}
+inline void banded_needs_table(bool overflow) {
+    if (overflow)
+        throw std::runtime_error("seqalib: banded calls take batches of at most " + std::to_string(kBandedMaxSymbols) +
+                                 " distinct symbols (the per-pair match bitmaps have no banded variant)");
+}
 using ChunkFn = std::function<void(size_t, size_t)>;
 inline void chunk_tramp(void* user, uint32_t p0, uint32_t p1) { (*static_cast<ChunkFn*>(user))(p0, p1); }
 
@@ -389,7 +407,7 @@ template <typename Ty, typename ContainerType, typename MatchFnTy>
 void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
            std::vector<sa_result>& res, raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off,
-           uint32_t chunks = 0, ChunkFn on_chunk = nullptr) {
+           uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand) {
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -397,6 +415,7 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     std::vector<uint64_t>&o1 = pk.o1, &o2 = pk.o2;
     raw_vector<uint8_t>&s1 = *pk.s1, &s2 = *pk.s2;
     tm.lap("symbol coding");
+    if (band != kNoBand) banded_needs_table(coder.overflow);
     if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
         align_bits<Ty>(algo, sc, fn, has_fn, pairs, res, ops, ops_off);
         if (on_chunk && !pairs.empty()) on_chunk(0, pairs.size());
@@ -411,7 +430,12 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     ops_off.resize(n);
     for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
     tm.lap("match table + buffers");
-    if (sa_multi* mg = multi_context()) {
+    if (band != kNoBand) {
+        check(sa_align_batch_banded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                    has_fn ? lut.data() : nullptr, band_arg(band), res.data(), ops.data(), cap),
+              "sa_align_batch_banded");
+        if (on_chunk && n) on_chunk(0, n);
+    } else if (sa_multi* mg = multi_context()) {
         const int rc = sa_multi_align_batch(mg, algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
                                             has_fn ? lut.data() : nullptr, res.data(), ops.data(), cap);
         if (rc != SA_OK)
@@ -439,7 +463,8 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
 // of pair p (start = -1, nops = 0).
 template <typename Ty, typename ContainerType, typename MatchFnTy>
 void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
-           const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res) {
+           const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
+           long long band = kNoBand) {
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -449,7 +474,15 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     tm.lap("symbol coding");
     const uint32_t n = (uint32_t)pairs.size();
     res.assign(n, sa_result{});
-    if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
+    if (band != kNoBand) {
+        banded_needs_table(coder.overflow);
+        std::vector<uint8_t> lut;
+        if (has_fn) lut = build_lut(coder, fn);
+        check(sa_score_batch_banded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                    has_fn ? lut.data() : nullptr, band_arg(band), res.data()),
+              "sa_score_batch_banded");
+        tm.lap("sa_score_batch_banded (GPU)");
+    } else if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
         std::vector<uint64_t> bo;
         std::vector<uint32_t> bits;
         match_bitmaps(fn, has_fn, pairs, o1, o2, bo, bits);

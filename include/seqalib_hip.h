@@ -232,6 +232,54 @@ int sa_multi_score_batch(sa_multi* multi, int algo, const sa_scoring* scoring,
                          const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
                          const uint8_t* match_lut, sa_result* results);
 
+/* Banded NW / SW: only the cells within `band` diagonals of the corner-to-corner corridor are
+ * computed, so a pair costs O((m + n) * B) cells and record bytes instead of O(m * n).
+ * For a pair of lengths m, n and half-width w = band, cell (i, j) (0 <= i <= m, 0 <= j <= n) is in
+ * the band when lo <= j - i <= hi with lo = min(0, n - m) - w, hi = max(0, n - m) + w, i.e.
+ * B = |n - m| + 2w + 1 diagonals; the band is per pair and always holds (0, 0) and (m, n).
+ * The recurrences, borders, tie rules, traceback order and op codes are those of sa_align_batch's
+ * SA_NW / SA_SW restricted to in-band cells: a candidate that would read a cell outside the band is
+ * no candidate (it never wins the maximum and never compares equal in the walk); in-band border
+ * cells keep i * gap / j * gap (NW) or 0 (SW); the SW end cell is the last in-band cell in row-major
+ * order holding the maximum.  With band >= max(m, n) the band is the whole matrix and every result
+ * field and op equals sa_align_batch's; for any band the score is <= the unbanded score.
+ * Arguments, argument checks, status codes, the blocking host-buffer contract, sa_ops_offset and the
+ * splitting into launches under sa_set_workspace_limit are sa_align_batch's / sa_score_batch's
+ * (score call: start = (-1, -1), nops = 0, reserved = 0, flags = 0, no walk, no records).
+ *   algo: SA_SW, SA_NW, or SA_HIRSCHBERG (= SA_NW); the affine algorithms: SA_ERR_UNSUPPORTED.
+ *   scoring: gap, match, mismatch, allow_mismatch.  allow_mismatch == 0 needs band >= 1
+ *     (band == 0: SA_ERR_UNSUPPORTED, a one-diagonal band has no other candidate).
+ *   band >= 2^31 (B overflows 32 bits): SA_ERR_ARG.
+ *   (These algorithm, scoring and band checks are made before the context is looked at, so they
+ *   give the same status with a NULL context; a NULL context with valid arguments: SA_ERR_ARG.)
+ *   SA_ERR_UNSUPPORTED also for a pair with
+ *     (m + n + 1) * max(|gap|, |match|, |mismatch|) >= 2^29 (mismatch counted only when allowed),
+ *     more than 4096 band diagonals inside its matrix (min(hi, n) - max(lo, -m) + 1: the band of a
+ *       pair lives in the registers of one wave),
+ *     SW: (m + 1) * that number of diagonals >= 2^31.
+ * sa_last_timings works after either call; sa_last_plan_ex reports SA_KERNEL_BANDED, the cells per
+ * lane and step of the widest variant the call used, 1 wave, and SA_RECORDS_BAND2 / SA_RECORDS_NONE.
+ * The small-call kernel is never used, whatever SEQALIB_TINY says. */
+int sa_align_batch_banded(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                          const uint8_t* seq1, const uint64_t* seq1_off,
+                          const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                          const uint8_t* match_lut, uint32_t band,
+                          sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_banded(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                          const uint8_t* seq1, const uint64_t* seq1_off,
+                          const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                          const uint8_t* match_lut, uint32_t band, sa_result* results);
+/* Plan of the banded path for a pair of max_m x max_n (host-only query, no device needed): cells per
+ * lane and step R, pairs per wave (4, 2 or 1), and the device workspace such a pair occupies in an
+ * align call's launch: its 2-bit records, (m + n + 2 - max(lo, -m)) * 2 R L / 8 bytes rounded up to
+ * L words, where 2 R L < 2 B is the variant's capacity in diagonals (at least 32) -- O((m + n) * B).
+ * This is what the pair needs: a workspace limit of this size is enough for it.  A call that joins
+ * two under-filled launches of neighbouring variants may let the pair occupy up to twice as much,
+ * and only while the limit leaves room for that.  A score call's pair occupies none.  Status codes as the calls' (SA_ERR_UNSUPPORTED: the shape is
+ * outside the limits above). */
+int sa_banded_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs,
+                         int* cells_per_lane, int* pairs_per_wave, uint64_t* workspace_bytes_per_pair);
+
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events
  * recorded on the stream they ran on: total fill-kernel ms, total traceback-kernel ms, and the
  * number of fill launches.  Waits for those events. */
@@ -254,6 +302,7 @@ int sa_last_kernel_timings(sa_ctx* ctx, float* fill_kernel_ms, float* fill_strea
  * in LDS), reading and writing pinned host memory.  Such a call reports 0 fill launches to
  * sa_last_timings.  Environment: SEQALIB_TINY=0 sends them through the batch kernels. */
 #define SA_KERNEL_TINY 3
+#define SA_KERNEL_BANDED 4   /* sa_align_batch_banded / sa_score_batch_banded */
 int sa_last_plan(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves);
 /* sa_last_plan plus what the fill stored for the traceback: SA_RECORDS_FLAGS (int32 equality
  * flags), SA_RECORDS_TAGS (T16 move tags per cell) or SA_RECORDS_SCORE_ONLY (score-only T16 SW fill:
@@ -263,6 +312,7 @@ int sa_last_plan(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves);
 #define SA_RECORDS_TAGS 1
 #define SA_RECORDS_SCORE_ONLY 2
 #define SA_RECORDS_NONE 3   /* score calls on the int32 / small-call kernels: the fill stored nothing for a traceback */
+#define SA_RECORDS_BAND2 4  /* banded align calls: 2 bits per in-band cell, laid out by anti-diagonal */
 int sa_last_plan_ex(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves, int* records);
 
 /* Plan of the int32 kernel for a batch (host-only query, no device needed): rows per lane R,

@@ -41,9 +41,11 @@ ALGO_NAMES = {SA_SW: "sw", SA_NW: "nw", SA_LOCAL_GOTOH: "local_gotoh", SA_GLOBAL
               SA_HIRSCHBERG: "hirschberg", SA_MYERS_MILLER: "myers_miller"}
 SA_FLAG_DIVERGED, SA_FLAG_BAD_SHAPE, SA_FLAG_SIZE_HACK, SA_FLAG_TIMEOUT = 1, 2, 4, 8
 SA_KERNEL_INT32, SA_KERNEL_T16, SA_KERNEL_T16_ENDCELL, SA_KERNEL_TINY = 0, 1, 2, 3
+SA_KERNEL_BANDED = 4    # banded calls (sa_align_batch_banded / sa_score_batch_banded)
 SA_PIPELINE_DEPTH = 2   # pipelined device calls that may run at once (distinct output buffers)
 SA_RECORDS_FLAGS, SA_RECORDS_TAGS, SA_RECORDS_SCORE_ONLY = 0, 1, 2
 SA_RECORDS_NONE = 3   # score calls on the int32 / small-call kernels: nothing stored for a traceback
+SA_RECORDS_BAND2 = 4  # banded align calls: 2 bits per in-band cell, laid out by anti-diagonal
 SA_HOOK_HAND_TAG, SA_HOOK_POISON_WS, SA_HOOK_F16 = 1, 2, 3   # sa_test_hook (tests only)
 INT32_MIN = -(2 ** 31)
 
@@ -135,6 +137,11 @@ def load_library():
     L.sa_score_batch_bits.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, C.c_uint32, vp, vp, vp]
     L.sa_score_batch_device.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32,
                                         C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_align_batch_banded.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32,
+                                        vp, vp, C.c_uint64]
+    L.sa_score_batch_banded.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32,
+                                        vp]
+    L.sa_banded_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p]
     L.sa_score_plan_query.argtypes = [C.c_int, C.POINTER(_Scoring), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                       i32p, i32p, i32p, u64p]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
@@ -154,6 +161,7 @@ def load_library():
                "sa_multi_create", "sa_multi_align_batch", "sa_score_batch", "sa_score_batch_bits",
                "sa_score_batch_device", "sa_multi_score_batch", "sa_score_plan_query",
                "sa_last_timings", "sa_last_kernel_timings", "sa_last_plan", "sa_last_plan_ex", "sa_plan_query", "sa_plan_query_ex", "sa_synth_dna", "sa_synth_mutate", "sa_synth_dna_batch",
+               "sa_align_batch_banded", "sa_score_batch_banded", "sa_banded_plan_query",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -304,6 +312,13 @@ def expand_ops(algo: int, s1: Sequence, s2: Sequence, r: PairResult, blank="-",
 
 
 # ---------------------------------------------------------------------------------- engine
+def _band_arg(band) -> int:
+    band = int(band)
+    if band < 0 or band > 0xFFFFFFFF:
+        raise SeqalibError(f"band must be in [0, 2^32): {band}")
+    return band
+
+
 def _as_bytes(s) -> bytes:
     if isinstance(s, (bytes, bytearray)):
         return bytes(s)
@@ -435,6 +450,66 @@ class Engine:
                                    npairs, lut_p, _ptr(res), _ptr(ops), ops_cap)
         self._check(rc, "sa_align_batch")
         return res[:npairs], ops
+
+    def align_banded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                            s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None):
+        """Banded host-buffer batch (sa_align_batch_banded): NW / SW over the cells within `band`
+        diagonals of each pair's corner-to-corner corridor.  Returns (results, ops) as align_packed."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        ops = np.zeros(ops_cap, dtype=np.uint8)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_align_batch_banded(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                          npairs, lut_p, _band_arg(band), _ptr(res), _ptr(ops), ops_cap)
+        self._check(rc, "sa_align_batch_banded")
+        return res[:npairs], ops
+
+    def score_banded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                            s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Banded score batch (sa_score_batch_banded): the results array (start = -1, nops = 0)."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_score_batch_banded(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                          npairs, lut_p, _band_arg(band), _ptr(res))
+        self._check(rc, "sa_score_batch_banded")
+        return res[:npairs]
+
+    def align_banded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                     lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the banded call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        res, ops = self.align_banded_packed(algo, scoring, s1, off1, s2, off2, band, lut)
+        out = []
+        for p in range(len(pairs)):
+            o = int(off1[p] + off2[p]) + p
+            r = res[p]
+            out.append(PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]),
+                                  int(r["start_j"]), int(r["flags"]), ops[o:o + int(r["nops"])].tobytes()))
+        return out
+
+    def score_banded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                     lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the banded call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_banded_packed(algo, scoring, s1, off1, s2, off2, band, lut))
 
     def align_bits(self, algo: int, scoring: ScoringSystem, off1: np.ndarray, off2: np.ndarray, bits: np.ndarray,
                    bits_off: np.ndarray):
@@ -619,6 +694,17 @@ def plan_query_ex(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, n
     return k.value, R.value, W.value, ws.value
 
 
+def banded_plan_query(algo: int, max_m: int, max_n: int, band: int, npairs: int = 1):
+    """(cells per lane and step, pairs per wave, workspace bytes per pair) of the banded path for a
+    pair of max_m x max_n at half-width `band` (sa_banded_plan_query).  Raises outside its limits."""
+    L = load_library()
+    R, ppw, ws = C.c_int(), C.c_int(), C.c_uint64()
+    rc = L.sa_banded_plan_query(algo, max_m, max_n, _band_arg(band), npairs, C.byref(R), C.byref(ppw), C.byref(ws))
+    if rc:
+        raise SeqalibError(f"sa_banded_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
+    return R.value, ppw.value, ws.value
+
+
 def score_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 4):
     """plan_query_ex for a host score call (sa_score_plan_query): with nsym > 4 the record-free int32
     fill, whose workspace per pair holds no direction records.  SA_MYERS_MILLER raises."""
@@ -701,9 +787,14 @@ class _Aligner:
         al2 = sorted({c for _, b in pairs for c in _as_bytes(b)})
         return lut_from_fn(self.match_fn, al1, al2)
 
-    def getAlignments(self, pairs: Sequence[Tuple[object, object]]) -> List[AlignedSequence]:
+    def getAlignments(self, pairs: Sequence[Tuple[object, object]], band: Optional[int] = None) -> List[AlignedSequence]:
+        """band: half-width of the banded call (NeedlemanWunschSA, HirschbergSA = NW, SmithWatermanSA;
+        the other aligners raise SeqalibError); None: the unbanded path."""
         eng = _engine(self.device)
-        res = eng.align(self.ALGO, self.scoring, pairs, self._lut(pairs))
+        if band is None:
+            res = eng.align(self.ALGO, self.scoring, pairs, self._lut(pairs))
+        else:
+            res = eng.align_banded(self.ALGO, self.scoring, pairs, band, self._lut(pairs))
         out = []
         for (a, b), r in zip(pairs, res):
             if r.flags & SA_FLAG_DIVERGED:
@@ -715,30 +806,34 @@ class _Aligner:
         self.last = res[-1] if res else None
         return out
 
-    def getAlignment(self, seq1, seq2) -> AlignedSequence:
-        return self.getAlignments([(seq1, seq2)])[0]
+    def getAlignment(self, seq1, seq2, band: Optional[int] = None) -> AlignedSequence:
+        return self.getAlignments([(seq1, seq2)], band=band)[0]
 
     def getScore(self) -> Optional[int]:
         return None if self.last is None else self.last.score
 
-    def _score_results(self, pairs) -> List[PairResult]:
-        res = _engine(self.device).score(self.ALGO, self.scoring, pairs, self._lut(pairs))
+    def _score_results(self, pairs, band: Optional[int] = None) -> List[PairResult]:
+        if band is None:
+            res = _engine(self.device).score(self.ALGO, self.scoring, pairs, self._lut(pairs))
+        else:
+            res = _engine(self.device).score_banded(self.ALGO, self.scoring, pairs, band, self._lut(pairs))
         for r in res:
             if r.flags & SA_FLAG_TIMEOUT:
                 raise SeqalibError("device hand-off timed out; result invalid")
         self.last = res[-1] if res else None
         return res
 
-    def getScores(self, pairs: Sequence[Tuple[object, object]]) -> List[int]:
+    def getScores(self, pairs: Sequence[Tuple[object, object]], band: Optional[int] = None) -> List[int]:
         """The getScore() of every pair in one GPU pass with no traceback; getScore() afterwards is
-        the last pair's."""
-        return [r.score for r in self._score_results(pairs)]
+        the last pair's.  band: as getAlignments."""
+        return [r.score for r in self._score_results(pairs, band)]
 
 
 class _LocalAligner(_Aligner):
-    def getEndCells(self, pairs: Sequence[Tuple[object, object]]) -> List[Tuple[int, int]]:
-        """(MaxRow, MaxCol) of every pair -- the last row-major cell holding the maximum."""
-        return [(r.end_i, r.end_j) for r in self._score_results(pairs)]
+    def getEndCells(self, pairs: Sequence[Tuple[object, object]], band: Optional[int] = None) -> List[Tuple[int, int]]:
+        """(MaxRow, MaxCol) of every pair -- the last row-major cell holding the maximum (band: the
+        last in-band one)."""
+        return [(r.end_i, r.end_j) for r in self._score_results(pairs, band)]
 
 
 class SmithWatermanSA(_LocalAligner):

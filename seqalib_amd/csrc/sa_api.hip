@@ -2308,6 +2308,283 @@ int sa_score_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
     return device_batch(c, algo, sc, d1, o1, d2, o2, npairs, max_m, max_n, d_lut, d_res, nullptr, stream, true);
 }
 
+// ------------------------------------------------------------------------- banded calls
+// sa_align_batch_banded / sa_score_batch_banded (kernels: sa_banded.hip).  Every pair gets the fill
+// variant (cells per lane R, lanes per pair L) its clipped band fits; the pairs of one variant are
+// launched together, longest first, in as many launches as sa_set_workspace_limit leaves room for
+// their records.  A score call stores no records and launches no walk.
+
+// Algorithm, scoring and band checks shared with sa_banded_plan_query (c may be NULL).
+static int banded_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, uint32_t band) {
+    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
+    if (*algo < SA_SW || *algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
+    if (*algo == SA_LOCAL_GOTOH || *algo == SA_GLOBAL_GOTOH || *algo == SA_MYERS_MILLER)
+        return fail(c, SA_ERR_UNSUPPORTED, "banded calls support the linear-gap algorithms only (SA_SW, SA_NW, SA_HIRSCHBERG)");
+    if (*algo == SA_HIRSCHBERG) *algo = SA_NW;
+    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: |n - m| + 2 * band + 1 diagonals overflow 32 bits");
+    if (band == 0 && !sc->allow_mismatch)
+        return fail(c, SA_ERR_UNSUPPORTED, "band = 0 needs allow_mismatch (a one-diagonal band has no other candidate)");
+    return SA_OK;
+}
+
+// One pair's geometry and fill variant, or why the banded path does not take it.
+static int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t m, uint64_t n, uint32_t band,
+                            BandGeom* g, int* variant) {
+    if (m >= (1u << 24) || n >= (1u << 24)) return fail(c, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
+    auto a = [](int32_t x) { return (int64_t)(x < 0 ? -(int64_t)x : x); };
+    const int64_t big = std::max(std::max(a(sc->gap), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
+    if ((int64_t)(m + n + 1) * big >= kBandScoreLimit)
+        return fail(c, SA_ERR_UNSUPPORTED, "banded calls need (m + n + 1) * max(|gap|, |match|, |mismatch|) < 2^29");
+    *g = band_geom((int32_t)m, (int32_t)n, (int32_t)std::min(band, kBandMaxW));
+    *variant = band_variant(g->beff);
+    if (*variant < 0)
+        return fail(c, SA_ERR_UNSUPPORTED, "band of " + std::to_string(g->beff) + " diagonals inside the matrix exceeds the " +
+                                               std::to_string(kBandMaxDiagonals) + " one wave holds");
+    if (algo == SA_SW && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
+        return fail(c, SA_ERR_UNSUPPORTED, "banded SW needs (m + 1) * band diagonals < 2^31");
+    return SA_OK;
+}
+
+static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                        const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                        sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
+    // (the checks that need no context come first, so they answer without a device too)
+    int rc = banded_prologue(c, &algo, sc, band);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
+    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
+    if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
+    if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
+    for (uint32_t p = 0; p < npairs; ++p)
+        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
+    const uint64_t t1 = off1[npairs], t2 = off2[npairs];
+    const uint64_t ops_total = notb ? 0 : t1 + t2 + npairs;
+    if (ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer needs " + std::to_string(ops_total) + " bytes");
+    if (!npairs) return SA_OK;
+    SA_HIP(c, hipSetDevice(c->device));
+    if ((rc = order_after_last(c, c->stream))) return rc;
+    const uint32_t w = std::min(band, kBandMaxW);
+
+    // pairs by variant, longest first; record offsets restart at every launch
+    std::vector<uint64_t> words(npairs);
+    std::vector<uint32_t> bucket[kBandVariants];
+    for (uint32_t p = 0; p < npairs; ++p) {
+        BandGeom g;
+        int v = 0;
+        if ((rc = banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, &g, &v))) return rc;
+        words[p] = notb ? 0 : band_rec_words(g, v);
+        bucket[v].push_back(p);
+    }
+    // A launch of fewer waves than the device has SIMDs runs as long as one wave does, so two such
+    // launches in a row cost two of those where one launch of both costs one.  The pairs of a variant
+    // therefore join the NEXT variant (one step in (R, L): twice the diagonals, at most twice the
+    // records) when that variant is in use too, the joint launch still has at most a wave per SIMD,
+    // and every moved pair's records still fit the workspace budget; a pair moves at most one step
+    // (a variant that took pairs in stays where it is).  So a pair's records stay within twice what
+    // sa_banded_plan_query reports, and a call that fits the limit unmerged never fails merged.
+    // $SEQALIB_BAND_MERGE=0: every pair keeps the narrowest variant that holds it (tests).
+    const uint64_t budget_words = notb ? 0 : ws_budget(c) / 4;
+    const char* merge_env = getenv("SEQALIB_BAND_MERGE");
+    if (!(merge_env && merge_env[0] == '0')) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
+        const uint64_t simds = 4ull * (uint64_t)cus;
+        bool took_in = false;   // bucket[v] holds pairs moved up from v - 1
+        for (int v = 0; v + 1 < kBandVariants; ++v) {
+            const bool fixed = took_in;
+            took_in = false;
+            if (fixed || bucket[v].empty() || bucket[v + 1].empty()) continue;
+            const uint64_t ppw = (uint64_t)(kWave / kBandL[v + 1]);
+            if ((bucket[v].size() + bucket[v + 1].size() + ppw - 1) / ppw > simds) continue;
+            std::vector<uint64_t> moved(bucket[v].size(), 0);
+            bool fits = true;
+            for (size_t k = 0; k < bucket[v].size() && !notb && fits; ++k) {
+                const uint32_t p = bucket[v][k];
+                const BandGeom g = band_geom((int32_t)(off1[p + 1] - off1[p]), (int32_t)(off2[p + 1] - off2[p]), (int32_t)w);
+                moved[k] = band_rec_words(g, v + 1);
+                fits = moved[k] <= budget_words;
+            }
+            if (!fits) continue;
+            for (size_t k = 0; k < bucket[v].size(); ++k) {
+                words[bucket[v][k]] = moved[k];
+                bucket[v + 1].push_back(bucket[v][k]);
+            }
+            bucket[v].clear();
+            took_in = true;
+        }
+    }
+    struct Launch { int v; uint32_t first, count; };
+    std::vector<Launch> launches;
+    std::vector<uint32_t> idx;
+    std::vector<uint64_t> recoff;
+    idx.reserve(npairs);
+    recoff.reserve(npairs);
+    uint64_t ws_words = 0;
+    int top_v = 0;
+    for (int v = 0; v < kBandVariants; ++v) {
+        std::vector<uint32_t>& b = bucket[v];
+        if (b.empty()) continue;
+        top_v = v;
+        std::stable_sort(b.begin(), b.end(), [&](uint32_t x, uint32_t y) {
+            return off1[x + 1] - off1[x] + off2[x + 1] - off2[x] > off1[y + 1] - off1[y] + off2[y + 1] - off2[y];
+        });
+        Launch cur{v, (uint32_t)idx.size(), 0};
+        uint64_t used = 0;
+        for (uint32_t p : b) {
+            if (!notb && words[p] > budget_words)
+                return fail(c, SA_ERR_NOMEM, "the band records of one pair (" + std::to_string(words[p] * 4) +
+                                                 " bytes) exceed the workspace limit");
+            if (cur.count && used + words[p] > budget_words) {
+                launches.push_back(cur);
+                cur = Launch{v, (uint32_t)idx.size(), 0};
+                used = 0;
+            }
+            idx.push_back(p);
+            recoff.push_back(used);
+            used += words[p];
+            cur.count++;
+            ws_words = std::max(ws_words, used);
+        }
+        launches.push_back(cur);
+    }
+    if (!notb && (rc = ensure_ws(c, std::max<uint64_t>(ws_words * 4, 256)))) return rc;
+
+    const bool use_lut = lut && !lut_is_identity(lut);
+    std::vector<uint32_t> bits;
+    if (use_lut) {
+        bits.assign(2048, 0);
+        for (int a = 0; a < 256; ++a)
+            for (int b = 0; b < 256; ++b)
+                if (lut[a * 256 + b]) bits[a * 8 + b / 32] |= 1u << (b % 32);
+    }
+    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
+    const uint64_t b_s1 = al(t1 + 1), b_s2 = al(t2 + 1), b_o = al(8ull * (npairs + 1)), b_res = al(sizeof(sa_result) * (uint64_t)npairs);
+    const uint64_t b_ops = al(ops_total + 1), b_bits = al(8192), b_idx = al(4ull * npairs), b_ro = al(8ull * npairs);
+    if ((rc = ensure_io(c, b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_bits + b_idx + b_ro))) return rc;
+    uint8_t* q = c->io;
+    uint8_t* const d1 = q; q += b_s1;
+    uint8_t* const d2 = q; q += b_s2;
+    uint64_t* const do1 = reinterpret_cast<uint64_t*>(q); q += b_o;
+    uint64_t* const do2 = reinterpret_cast<uint64_t*>(q); q += b_o;
+    sa_result* const dres = reinterpret_cast<sa_result*>(q); q += b_res;
+    uint8_t* const dops = q; q += b_ops;
+    uint32_t* const dbits = reinterpret_cast<uint32_t*>(q); q += b_bits;
+    uint32_t* const didx = reinterpret_cast<uint32_t*>(q); q += b_idx;
+    uint64_t* const dro = reinterpret_cast<uint64_t*>(q);
+    hipStream_t st = c->stream;
+    if (t1) SA_HIP(c, hipMemcpyAsync(d1, seq1, t1, hipMemcpyHostToDevice, st));
+    if (t2) SA_HIP(c, hipMemcpyAsync(d2, seq2, t2, hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(do1, off1, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(do2, off2, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
+    if (use_lut) SA_HIP(c, hipMemcpyAsync(dbits, bits.data(), 8192, hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(didx, idx.data(), 4ull * npairs, hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(dro, recoff.data(), 8ull * npairs, hipMemcpyHostToDevice, st));
+
+    const bool kernel_timing = getenv("SEQALIB_KERNEL_TIMING") != nullptr;
+    c->launches = 0;
+    c->kvars.clear();
+    c->timed_stream = st;
+    c->tb_kernels = 0;
+    for (const Launch& ln : launches) {
+        while ((int)c->events.size() < 3 * (c->launches + 1)) {
+            hipEvent_t ev;
+            SA_HIP(c, hipEventCreate(&ev));
+            c->events.push_back(ev);
+        }
+        hipEvent_t* ev = &c->events[3 * c->launches];
+        hipEvent_t* kev = nullptr;
+        if (kernel_timing) {
+            while ((int)c->kevents.size() < kKEv * (c->launches + 1)) {
+                hipEvent_t e;
+                SA_HIP(c, hipEventCreate(&e));
+                c->kevents.push_back(e);
+            }
+            c->kvars.resize(c->launches + 1);
+            c->kvars[c->launches] = 1;
+            kev = &c->kevents[kKEv * c->launches];
+        }
+        BandParams bp;
+        bp.seq1 = d1;
+        bp.off1 = do1;
+        bp.seq2 = d2;
+        bp.off2 = do2;
+        bp.lutbits = use_lut ? dbits : nullptr;
+        bp.idx = didx + ln.first;
+        bp.recoff = dro + ln.first;
+        bp.rec = reinterpret_cast<uint32_t*>(c->ws);
+        bp.res = dres;
+        bp.ops = dops;
+        bp.count = ln.count;
+        bp.band = w;
+        bp.gap = sc->gap;
+        bp.match = sc->match;
+        bp.mismatch = sc->allow_mismatch ? sc->mismatch : kBandNeg;
+        bp.allow = sc->allow_mismatch;
+        bp.R = kBandR[ln.v];
+        bp.L = kBandL[ln.v];
+        SA_HIP(c, hipEventRecord(ev[0], st));
+        if (kev) SA_HIP(c, hipEventRecord(kev[0], st));
+        SA_HIP(c, launch_banded_fill(algo, ln.v, use_lut, !notb, bp, st));
+        if (kev) SA_HIP(c, hipEventRecord(kev[1], st));
+        SA_HIP(c, hipEventRecord(ev[1], st));
+        if (!notb) {
+            SA_HIP(c, launch_banded_tb(algo, use_lut, bp, st));
+            c->tb_kernels++;
+        }
+        SA_HIP(c, hipEventRecord(ev[2], st));
+        c->launches++;
+    }
+    c->nvar = 1;
+    c->host_sel = -1;
+    c->var_kernel[0] = SA_KERNEL_BANDED;
+    c->var_R[0] = kBandR[top_v];
+    c->var_W[0] = 1;
+    c->var_records[0] = notb ? SA_RECORDS_NONE : SA_RECORDS_BAND2;
+
+    // outputs through the context's pinned staging, as the other host paths: [results][ops]
+    SA_HIP(c, c->ostage.alloc(b_res + ops_total));
+    sa_result* const sres = reinterpret_cast<sa_result*>(c->ostage.data());
+    uint8_t* const sops = c->ostage.data() + b_res;
+    SA_HIP(c, hipMemcpyAsync(sres, dres, sizeof(sa_result) * (uint64_t)npairs, hipMemcpyDeviceToHost, st));
+    if (!notb && ops_total) SA_HIP(c, hipMemcpyAsync(sops, dops, ops_total, hipMemcpyDeviceToHost, st));
+    if ((rc = mark_last(c, st))) return rc;
+    SA_HIP(c, hipStreamSynchronize(st));
+    memcpy(results, sres, sizeof(sa_result) * (uint64_t)npairs);
+    for (uint32_t p = 0; p < npairs && !notb; ++p) {
+        const uint64_t o = off1[p] + off2[p] + p;
+        memcpy(ops + o, sops + o, results[p].nops);
+    }
+    return SA_OK;
+}
+
+int sa_align_batch_banded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                          const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                          sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, false);
+}
+
+int sa_score_batch_banded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                          const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                          sa_result* results) {
+    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, nullptr, 0, true);
+}
+
+int sa_banded_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs, int* cells_per_lane,
+                         int* pairs_per_wave, uint64_t* ws_bytes_per_pair) {
+    (void)npairs;   // a pair's variant and records depend on its own shape only
+    // (the scoring-dependent checks are the calls'; a permissive scoring stands in for them here)
+    const sa_scoring any{0, 0, 0, 0, 0, 1};
+    int rc = banded_prologue(nullptr, &algo, &any, band);
+    if (rc) return rc;
+    BandGeom g;
+    int v = 0;
+    if ((rc = banded_pair_plan(nullptr, algo, &any, max_m, max_n, band, &g, &v))) return rc;
+    if (cells_per_lane) *cells_per_lane = kBandR[v];
+    if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
+    if (ws_bytes_per_pair) *ws_bytes_per_pair = band_rec_words(g, v) * 4;
+    return SA_OK;
+}
+
 int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,
                         int* kernel, int* R, int* W, uint64_t* ws_bytes_per_pair) {
     if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(nullptr, SA_ERR_ARG, "unknown algorithm");

@@ -358,4 +358,61 @@ struct TinyParams {
 // score: the kernel stops after the fill (no flag stores to LDS, no walk, no ops; the results follow
 // the score contract, include/seqalib_hip.h sa_score_batch)
 hipError_t launch_tiny(int algo, bool lut, int max_m, const TinyParams& p, hipStream_t stream, bool score = false);
+
+// The banded path (sa_banded.hip; sa_align_batch_banded / sa_score_batch_banded).
+// What a cell outside the band or the matrix holds.  The host admits only pairs whose scores stay
+// inside (-2^29, 2^29), so a candidate built from it is below every real score and does not wrap.
+constexpr int32_t kBandNeg = -(1 << 30);
+constexpr int32_t kBandScoreLimit = 1 << 29;
+// The half-width a call's `band` is clamped to (sequences are shorter than 2^24, so any larger band
+// is the whole matrix as well).
+constexpr uint32_t kBandMaxW = 1u << 25;
+// A pair's band clipped to its matrix: diagonals lo..hi (k = j - i), B' = beff of them; its sweep
+// runs over steps t = i + j - lo, records are kept from step tb (even) to tend = m + n - lo.
+struct BandGeom {
+    int32_t lo, hi, beff, tb, tend;
+};
+__host__ __device__ inline BandGeom band_geom(int32_t m, int32_t n, int32_t w) {
+    const int32_t d = n - m;
+    int32_t lo = (d < 0 ? d : 0) - w, hi = (d > 0 ? d : 0) + w;
+    if (lo < -m) lo = -m;
+    if (hi > n) hi = n;
+    return BandGeom{lo, hi, hi - lo + 1, (-lo) & ~1, m + n - lo};
+}
+// Fill variants: R cells per lane and step, L lanes per pair (64 / L pairs per wave); a variant holds
+// bands of up to 2 R L diagonals.  kBandMaxDiagonals is the widest (clipped) band the path takes.
+constexpr int kBandVariants = 8;
+constexpr int kBandR[kBandVariants] = {1, 2, 4, 4, 4, 8, 16, 32};
+constexpr int kBandL[kBandVariants] = {16, 16, 16, 32, 64, 64, 64, 64};
+constexpr int32_t kBandMaxDiagonals = 2 * 32 * 64;
+inline int band_variant(int32_t beff) {   // -1: wider than kBandMaxDiagonals
+    for (int v = 0; v < kBandVariants; ++v)
+        if (beff <= 2 * kBandR[v] * kBandL[v]) return v;
+    return -1;
+}
+// 32-bit record words of a pair: 2 bits per cell slot, step-major ([step group][lane]).
+inline uint64_t band_rec_words(const BandGeom& g, int v) {
+    const uint64_t steps = (uint64_t)(g.tend - g.tb) + 1;
+    const int R = kBandR[v], L = kBandL[v];
+    return R <= 16 ? (steps + 16 / R - 1) / (16 / R) * L : steps * 2 * L;
+}
+struct BandParams {
+    const uint8_t* seq1;
+    const uint64_t* off1;
+    const uint8_t* seq2;
+    const uint64_t* off2;
+    const uint32_t* lutbits;   // 256 x 8 words as FillParams::lutbits, or NULL (byte equality)
+    const uint32_t* idx;       // the pairs of this launch (indices into off1 / off2 / res)
+    const uint64_t* recoff;    // per entry of idx: word offset of its records in rec
+    uint32_t* rec;
+    sa_result* res;
+    uint8_t* ops;
+    uint32_t count;
+    uint32_t band;             // half-width, <= kBandMaxW
+    int32_t gap, match, mismatch;   // mismatch: kBandNeg when mismatches are not allowed
+    int allow;
+    int R, L;                  // the variant that wrote rec (the walk)
+};
+hipError_t launch_banded_fill(int algo, int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
+hipError_t launch_banded_tb(int algo, bool lut, const BandParams& p, hipStream_t s);
 }  // namespace sa

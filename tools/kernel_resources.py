@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Register and scratch use of every fill_kernel instantiation of a translation unit, from the
-compiler's own resource-usage remarks (no GPU needed).
+"""Register and scratch use of every fill_kernel and banded_fill_kernel instantiation of a translation
+unit, from the compiler's own resource-usage remarks (no GPU needed).
 
     tools/kernel_resources.py seqalib_amd/csrc/sa_fill_sw_score.hip [more units ...] > table.txt
     tools/kernel_resources.py --parse remarks.txt ...      # remarks captured earlier
@@ -16,7 +16,8 @@ HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-device-only",
          "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
 NAME = re.compile(r"Function Name: _ZN2sa11fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
-FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
+FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
+BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E")
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
 MM = ["eq", "lut", "bits"]
 
@@ -36,6 +37,11 @@ def parse(text):
             cur = {"args": tuple(int(x) for x in m.groups())}
             rows.append(cur)
             continue
+        m = BANDED.search(line)
+        if m:   # the banded fills (sa_banded.hip): algorithm, R, L, LUT, REC
+            cur = {"banded": tuple(int(x) for x in m.groups())}
+            rows.append(cur)
+            continue
         if "Function Name:" in line:
             cur = None
             continue
@@ -51,7 +57,20 @@ def main(argv):
     rows = []
     for f in files:
         rows += parse(open(f).read() if parse_only else remarks(f))
+    banded = sorted((r for r in rows if "banded" in r), key=lambda r: r["banded"])
+    rows = [r for r in rows if "args" in r]
     rows.sort(key=lambda r: r["args"])
+    if banded:
+        print(f"{'banded':<8}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
+        bad_banded = 0
+        for r in banded:
+            alg, R, L, lut, rec = r["banded"]
+            print(f"{ALG[alg]:<8}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
+                  f"{r['Occupancy']:>6}{r['LDS']:>7}")
+            bad_banded += r["ScratchSize"] != 0
+        print(f"# {len(banded)} banded kernels, {bad_banded} with scratch")
+        if not rows:
+            return 1 if bad_banded else 0
     print(f"{'algorithm':<12}{'R':>3} {'match':<5}{'allow':>6}{'keyed':>6} {'plan':<6}{'norec':>6}{'VGPRs':>6}{'SGPRs':>6}"
           f"{'scratch':>8}{'waves':>6}{'LDS':>7}")
     bad = 0
@@ -63,7 +82,7 @@ def main(argv):
               f"{r['VGPRs']:>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}{r['Occupancy']:>6}{r['LDS']:>7}")
         bad += r["ScratchSize"] != 0
     print(f"# {len(rows)} kernels, {bad} with scratch")
-    return 1 if bad else 0
+    return 1 if bad or (banded and bad_banded) else 0
 
 
 if __name__ == "__main__":
