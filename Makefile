@@ -57,6 +57,7 @@ clean:
 	$(MAKE) -C oracle clean
 
 # A/B variant of the engine: make variant V=name DEFS="-DSOMETHING" -> seqalib_amd/lib/ab/lib<name>.so
+# (two-pairs-per-wave fill: -DSA_SO2_NO_TAB no column table in LDS, -DSA_SO2_NO_CML3 the two-op chunk maximum)
 variant:
 	@mkdir -p build/ab_$(V) seqalib_amd/lib/ab
 	printf '%s\n' $(HIP_SRCS) $(CPP_SRCS) | xargs -P 8 -I{} sh -c '$(HIPCC) $(HIPFLAGS) $(DEFS) -c {} -o build/ab_$(V)/$$(basename {}).o'

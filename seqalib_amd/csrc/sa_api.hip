@@ -1101,6 +1101,16 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                 const uint32_t range = std::max((nch + sg - 1) / sg, 3u) * kChunk + kWave;
                 const uint32_t cap = (range + 15) & ~15u;
                 fp.so2_stage = (2 * cap <= 8192 && !no_stage) ? cap : 0;
+                // ... or, where 8 bytes per column fit the same 8 KiB, for the unit's column table
+                // (with the 896-byte step buffer 16 units per CU stay within 160 KiB of LDS, so the
+                // table never lowers the kernel's 3 or 4 waves per SIMD)
+#ifndef SA_SO2_NO_TAB
+                const char* tab_env = getenv("SEQALIB_SO2_TAB");
+                if (fp.so2_stage && 8 * cap <= 8192 && !(tab_env && tab_env[0] == '0')) {
+                    fp.so2_tab = cap;
+                    fp.so2_stage = 0;
+                }
+#endif
                 if (const uint32_t cell = v.t16 ? so2_f16_scoring(c, algo, sc, tm) : 0u) {
                     fp.so2_f16 = cell;
                     fp.retry_above = std::min(fp.retry_above, kSo2F16RetryAbove);

@@ -65,6 +65,12 @@
 // ONE packed multiply by 2^-13 (k 2^-24 has the bit pattern k: f16 denormals are on) and band rows
 // come back through one by 2^13: no sub-dword (SDWA / op_sel) write anywhere in this cell.
 //
+// TAB: the column table words {A, B} of every column the unit runs, built once per unit in LDS and
+// read per lane and step (one ds_read_b64 at an immediate offset) where !TAB shifts them down the
+// lanes with two v_mov_b32_dpp per step and stages 32 columns per chunk; the host picks TAB whenever
+// the widest unit range of the launch fits 8 KiB (1,024 columns; the headline's is 608).  The f16
+// cells take the chunk maximum of two rows in one v_pk_maximum3_f16 (values >= 0, from +0.0).
+//
 // ALG = SA_NW (round 6): the same cell without the clamp (SANeedlemanWunsch.h:69-86; registers hold
 // H - delta, the T16 window of t16_mode), the borders i Gap - delta / j Gap - delta in the left
 // column, the corner and band 0's top row, no chunk maxima.  H[m][n] of each pair is taken at the
@@ -102,10 +108,21 @@ __device__ __forceinline__ uint32_t wave_pk_max(uint32_t v) {
     v = pk_max_u16(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
     return v;
 }
-__device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
+[[maybe_unused]] __device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
     uint32_t d;
     asm("v_pk_max_i16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
     return d;
+}
+// both halves: max(a, b, c) of f16 values >= 0 (the chunk maximum of the f16 cells, one op for two
+// rows; SA_SO2_NO_CML3: the two integer maxima it replaces, for A/B builds)
+__device__ __forceinline__ uint32_t pk_max3_f16(uint32_t a, uint32_t b, uint32_t c) {
+#ifdef SA_SO2_NO_CML3
+    return pk_max_i16(pk_max_i16(a, b), c);
+#else
+    uint32_t d;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+#endif
 }
 // both halves: f16 integer -> u16 integer, and back.  (A dst_sel write followed at once by a VALU
 // read of the register -- the second conversion's UNUSED_PRESERVE read, the statement's first
@@ -169,7 +186,7 @@ constexpr int so2_waves(int FK, int R) { return FK == 2 && R == 32 ? 3 : 4; }
 
 }  // namespace
 
-template <int ALG, int R, int FK>
+template <int ALG, int R, int FK, bool TAB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(so2_waves(FK, R), so2_waves(FK, R))))
 void fill_so2_kernel(FillParams P) {
     constexpr bool NWK = ALG == SA_NW;
@@ -181,8 +198,9 @@ void fill_so2_kernel(FillParams P) {
     constexpr int SPP = 8;   // steps per 16-byte edge-stream packet (16 bits per lane-step)
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     // step buffer: [0, 32) lane 0's row-above input (A | B << 16) of the chunk's steps, [32, 96)
-    // the column table words (A, B interleaved), [96, 128) the last row parked by lane 63 per step,
-    // [160, 192) the discard slots of lanes 0..62's parking writes
+    // the column table words (A, B interleaved; !TAB only), [96, 128) the last row parked by lane 63
+    // per step, [160, 192) the discard slots of lanes 0..62's parking writes; behind it the unit's
+    // Seq2 codes (so2_stage) or its column table (TAB)
     uint32_t* const s_step = smem;
     const int lane = threadIdx.x;
     uint32_t* const s_park = s_step + (lane == 63 ? 96 : 160);
@@ -277,6 +295,23 @@ void fill_so2_kernel(FillParams P) {
         wa = ia ? (xa == 0 ? cw[0] : xa == 1 ? cw[1] : xa == 2 ? cw[2] : cw[3]) : kOut;
         wb = ib ? (xb == 0 ? cw[0] : xb == 1 ? cw[1] : xb == 2 ? cw[2] : cw[3]) : kOut;
     };
+    // TAB: the unit's column table (P.so2_tab entries of LDS behind the step buffer; the host sizes
+    // it for the widest range a unit of the launch may run, sa_api.hip): entry e = {A word, B word}
+    // of column kb + e, for the columns [kb, 32 c1) -- the 64 before the unit's first chunk
+    // included; 0 left of column 0, the state the lanes' column words start from on the DPP path.
+    // Lane t reads its column kC + q - t at step q with one 8-byte LDS load, so no column word
+    // travels down the lanes (two DPP moves per step) and no chunk stages its own.
+    const int kb = (int)(c0 * kChunk) - kWave;
+    const uint32_t tab_n = (c1 > c0 ? c1 - c0 : 0u) * kChunk + kWave;
+    uint2* const s_tab = reinterpret_cast<uint2*>(smem + kStepBufWords);
+    if constexpr (TAB) {
+        for (uint32_t e = (uint32_t)lane; e < min(tab_n, P.so2_tab); e += kWave) {
+            uint32_t wa = 0, wb = 0;
+            if (kb + (int)e >= 0) col_pair(kb + (int)e, wa, wb);
+            s_tab[e] = make_uint2(wa, wb);
+        }
+        __syncthreads();
+    }
     // (FK: the packed f16 Gap)
     const uint32_t G128 = X4   ? f16_bits_sc(G) * 0x10001u
                           : FK ? f16_bits(G) * 0x10001u
@@ -334,10 +369,11 @@ void fill_so2_kernel(FillParams P) {
             pb_ = liveB ? __hip_atomic_load(hsB + (uint32_t)(R * kWave + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : epoch16;
         };
         auto stale = [&]() __attribute__((always_inline)) -> bool {
-            bool st = ((pa_ & 0xffff0000u) != epoch16) | ((pb_ & 0xffff0000u) != epoch16);
+            // (the tag bits that differ in any word, folded; one test)
+            uint32_t x = (pa_ ^ epoch16) | (pb_ ^ epoch16);
 #pragma unroll
-            for (int r = 0; r < R; ++r) st |= ((Hp[r] & 0xffff0000u) != epoch16) | ((sel[r] & 0xffff0000u) != epoch16);
-            return st;
+            for (int r = 0; r < R; ++r) x |= (Hp[r] ^ epoch16) | (sel[r] ^ epoch16);
+            return (x >> 16) != 0;
         };
         rd();
         for (uint32_t it = 0; !seg_lost && __builtin_amdgcn_ballot_w64(stale()) != 0; ++it) {
@@ -352,7 +388,7 @@ void fill_so2_kernel(FillParams P) {
             for (int r = 0; r < R; ++r) Fr[r] = pk_addg_clamp(Hp[r], G128);
         }
         prev_up = lo16(pa_) | pb_ << 16;
-        col_pair((int)(c0 * kChunk) - 1 - lane, colA, colB);
+        if (!TAB) col_pair((int)(c0 * kChunk) - 1 - lane, colA, colB);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -365,18 +401,24 @@ void fill_so2_kernel(FillParams P) {
     // One step of the chunk at kC: lane t computes column j = kC + q - t of its R rows of both
     // pairs (RAMP: a lane left of its first column keeps its border state).
     // (sq = s_step + q0, sc = s_step + 32 + 2 q0, g the step in its packet: one LDS address per
-    // packet and array, immediate offsets)
-    auto step = [&](auto ramp, auto gc, int kC, int q0, const uint32_t* sq, const uint32_t* sc, uint32_t* sp,
-                    uint32_t& recA, uint32_t& recB) {
+    // packet and array, immediate offsets.  TAB: tp = the lane's column table entry of step q0)
+    auto step = [&](auto ramp, auto gc, int kC, int q0, const uint32_t* sq, const uint32_t* sc,
+                    const uint2* tp, uint32_t* sp, uint32_t& recA, uint32_t& recB) {
         constexpr bool RAMP = decltype(ramp)::value;
         constexpr int g = decltype(gc)::value;
         constexpr int PH = g & 3;
         const int q = q0 + g;
         const uint32_t vh = sq[g];
-        const uint32_t va = sc[2 * g], vb = sc[2 * g + 1];
         const uint32_t up = (uint32_t)shr1((int)vh, (int)Hp[R - 1]);
-        colA = (uint32_t)shr1((int)va, (int)colA);
-        colB = (uint32_t)shr1((int)vb, (int)colB);
+        if constexpr (TAB) {
+            const uint2 cwd = tp[g];
+            colA = cwd.x;
+            colB = cwd.y;
+        } else {
+            const uint32_t va = sc[2 * g], vb = sc[2 * g + 1];
+            colA = (uint32_t)shr1((int)va, (int)colA);
+            colB = (uint32_t)shr1((int)vb, (int)colB);
+        }
         if (!RAMP || kC + q - lane >= 0) {
             uint32_t dcur, pt;
             if constexpr (FK)
@@ -453,9 +495,8 @@ void fill_so2_kernel(FillParams P) {
                 // fill_so_kernel).  Valid in ramp chunks too: the cells right of the matrix edge
                 // follow the recurrence (substitution -128), so the bound holds through them.
                 if (!NWK && PH == 3 && (r & 7) == 7) {
-                    if constexpr (FK) {   // (f16 patterns of H >= 0; a -0.0 is the smallest i16)
-                        cml = pk_max_i16(cml, Hp[r - 4]);
-                        cml = pk_max_i16(cml, Hp[r]);
+                    if constexpr (FK) {   // (f16 values >= 0, cml from +0.0: a -0.0 never wins)
+                        cml = pk_max3_f16(cml, Hp[r - 4], Hp[r]);
                     } else {
                         cml = pk_max_u16(cml, Hp[r - 4]);
                         cml = pk_max_u16(cml, Hp[r]);
@@ -507,7 +548,7 @@ void fill_so2_kernel(FillParams P) {
             const int c = kC + (int)ln;
             const bool in = lane < kChunk;
             uint32_t wa = 0, wb = 0;
-            if (in) col_pair(c, wa, wb);
+            if (in && !TAB) col_pair(c, wa, wb);
             const bool wantA = in && band0 > 0 && liveA && c < nA, wantB = in && band0 > 0 && liveB && c < nB;
             gu32* const ga = gA + (uint32_t)c;
             gu32* const gb = gB + (uint32_t)c;
@@ -528,8 +569,10 @@ void fill_so2_kernel(FillParams P) {
             if (in) {
                 const uint32_t hab = lo16(ha) | hb << 16;
                 s_step[ln] = X4 ? u16x2_to_sc(hab) : FK ? u16x2_to_f16x2(hab) : hab;
-                s_step[32 + 2 * ln] = wa;
-                s_step[33 + 2 * ln] = wb;
+                if (!TAB) {
+                    s_step[32 + 2 * ln] = wa;
+                    s_step[33 + 2 * ln] = wb;
+                }
             }
         }
         __syncthreads();
@@ -540,10 +583,11 @@ void fill_so2_kernel(FillParams P) {
             uint32_t pa[SPP / 2] = {0, 0, 0, 0}, pb[SPP / 2] = {0, 0, 0, 0};
             const uint32_t* const sq = s_step + q0;
             const uint32_t* const sc = s_step + 32 + 2 * q0;
+            const uint2* const tp = s_tab + (kC - kb + q0 - lane);   // (>= 1: kC - kb >= 64)
             uint32_t* const sp = s_park + q0;
             auto st = [&](auto gc) __attribute__((always_inline)) {
                 constexpr int g = decltype(gc)::value;
-                step(rmp, gc, kC, q0, sq, sc, sp, pa[g / 2], pb[g / 2]);
+                step(rmp, gc, kC, q0, sq, sc, tp, sp, pa[g / 2], pb[g / 2]);
             };
             st(std::integral_constant<int, 0>{});
             st(std::integral_constant<int, 1>{});
@@ -735,11 +779,14 @@ void fill_so2_kernel(FillParams P) {
 }
 
 hipError_t launch_fill_so2(int algo, int R, const FillParams& p, uint32_t grid, hipStream_t stream) {
-    const size_t lds = (size_t)kStepBufWords * 4 + 2 * (size_t)p.so2_stage;
-#define SO2_LAUNCH(A, RR, F)                                                                        \
-    if (algo == (A) && R == (RR) && (int)p.so2_f16 == (F)) {                                        \
-        hipLaunchKernelGGL((fill_so2_kernel<A, RR, F>), dim3(grid), dim3(kWave), lds, stream, p);  \
-        return hipGetLastError();                                                                  \
+    const size_t lds = (size_t)kStepBufWords * 4 + std::max(2 * (size_t)p.so2_stage, 8 * (size_t)p.so2_tab);
+#define SO2_LAUNCH(A, RR, F)                                                                              \
+    if (algo == (A) && R == (RR) && (int)p.so2_f16 == (F)) {                                              \
+        if (p.so2_tab)                                                                                   \
+            hipLaunchKernelGGL((fill_so2_kernel<A, RR, F, true>), dim3(grid), dim3(kWave), lds, stream, p);  \
+        else                                                                                             \
+            hipLaunchKernelGGL((fill_so2_kernel<A, RR, F, false>), dim3(grid), dim3(kWave), lds, stream, p); \
+        return hipGetLastError();                                                                        \
     }
     SO2_LAUNCH(SA_SW, 32, 2)
     SO2_LAUNCH(SA_SW, 16, 2)

@@ -109,6 +109,10 @@ struct FillParams {
     // the two-pairs-per-wave SW fill (sa_fill_so2.hip): bytes of LDS per pair for its unit's Seq2
     // symbol codes (0: read from global memory per chunk)
     uint32_t so2_stage;
+    // ... or entries (8 bytes: the column's table words of both pairs) of LDS for its unit's column
+    // table, read per lane and step; then so2_stage is 0.  0: the table words travel down the
+    // lanes by DPP (ranges too wide for the LDS budget, $SEQALIB_SO2_TAB=0)
+    uint32_t so2_tab;
     // its f16 cells (SW; every value exact below 2048, pairs above kSo2F16RetryAbove re-run): 1 the
     // 5-op cell on f16 integers, 2 the 4-op cell on values scaled by 2^-11 with F kept per row
     uint32_t so2_f16;

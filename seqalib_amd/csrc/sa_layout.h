@@ -53,6 +53,11 @@ static_assert(kLagPhases == 3 && kRing >= 4 * kChunk, "re-derive the ring bound"
 //   [0, 32) lane-0 row-above input of the chunk's steps, [32, 64) its Ix (affine),
 //   [64, 96) the column symbols, [96, 128) the band's last row parked per step (H),
 //   [128, 160) the same for Ix, [160, 224) the discard target of lanes 0..62's parking writes.
+// The two-pairs-per-wave fill (sa_fill_so2.hip) uses one such buffer its own way: [0, 32) the row
+// above (A | B << 16), [32, 96) the chunk's column table words (A, B interleaved) on the DPP path
+// only, [96, 128) the parked last row, [160, 192) the discard slots; behind the buffer either the
+// unit's Seq2 codes (2 x FillParams::so2_stage bytes) or the unit's column table (FillParams::so2_tab
+// 8-byte entries {A word, B word}, one per column from 64 before the unit's first chunk on).
 constexpr int kStepBufWords = 224;
 // Dynamic LDS of the fill kernel: [match bits (LUT)][hand-off rings][step buffers][staged Seq2].
 struct LdsLayout {

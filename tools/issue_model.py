@@ -12,7 +12,8 @@ instruction at its measured issue rate and reports
     cycles_per_lane_cell = sum(count / rate) / cells_per_lane_in_block   [SIMD cycles / 64 cells]
     peak_gcups = SIMDs * clock * 64 / cycles_per_lane_cell / 1e9
 Scalar and memory instructions issue on other units and are not charged.
-    python3 tools/issue_model.py [--out profiles/issue_model_r03.json]
+    python3 tools/issue_model.py [--out profiles/issue_model_r03.json] [--kernels label,label]
+With --kernels, an existing --out file keeps its other kernels' entries.
 """
 import argparse, collections, json, os, re, subprocess, sys, tempfile
 
@@ -38,13 +39,16 @@ KERNELS = {  # label -> (TU, mangled name, cells per lane in one steady block = 
     # round 6: the score-only SW fill with two pairs per wave (fill_so2_kernel<R>, sa_fill_so2.hip)
     # (fill_so2_kernel<ALG, R, FK>; FK: the f16 cell, the default for SW at f16-exact scorings)
     # (FK = 2: the 4-op scaled-f16 cell, the default since it shipped; the labels bench.py reads stay)
-    "sw_so2f_r32": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi2EEEvNS_10FillParamsE", 512),   # 8 steps x 32 rows x 2 pairs
-    "sw_so2f_r16": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi16ELi2EEEvNS_10FillParamsE", 256),
+    # (TAB = 1: the unit's column table in LDS, the path every launch takes whose unit ranges fit;
+    # _dpp: the fallback whose column words travel down the lanes)
+    "sw_so2f_r32": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi2ELb1EEEvNS_10FillParamsE", 512),   # 8 steps x 32 rows x 2 pairs
+    "sw_so2f_r16": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi16ELi2ELb1EEEvNS_10FillParamsE", 256),
+    "sw_so2f_r32_dpp": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi2ELb0EEEvNS_10FillParamsE", 512),
     # (FK = 1: the 5-op f16 cell, SEQALIB_SO2_F16=5)
-    "sw_so2f5_r32": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi1EEEvNS_10FillParamsE", 512),
-    "sw_so2f5_r16": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi16ELi1EEEvNS_10FillParamsE", 256),
-    "sw_so2_r32": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi0EEEvNS_10FillParamsE", 512),
-    "sw_so2_r16": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi16ELi0EEEvNS_10FillParamsE", 256),
+    "sw_so2f5_r32": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi1ELb1EEEvNS_10FillParamsE", 512),
+    "sw_so2f5_r16": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi16ELi1ELb1EEEvNS_10FillParamsE", 256),
+    "sw_so2_r32": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi32ELi0ELb1EEEvNS_10FillParamsE", 512),
+    "sw_so2_r16": ("sa_fill_so2.hip", "_ZN2sa15fill_so2_kernelILi0ELi16ELi0ELb1EEEvNS_10FillParamsE", 256),
     # round 5: the score-only fills (fill_so_kernel<ALG, R>): SW / NW band units, LG / GG affine
     "sw_so_r32": ("sa_fill_sw.hip", "_ZN2sa14fill_so_kernelILi0ELi32EEEvNS_10FillParamsE", 256),   # 8 steps x 32 rows
     "sw_so_r16": ("sa_fill_sw.hip", "_ZN2sa14fill_so_kernelILi0ELi16EEEvNS_10FillParamsE", 128),
@@ -103,6 +107,8 @@ def main():
     a = ap.parse_args()
     R = rates()
     out = {"rates_files": [os.path.relpath(f, ROOT) for f in RATES_FILES], "simds": SIMDS, "clock_hz": CLOCK, "kernels": {}}
+    if a.out and os.path.exists(a.out) and a.kernels != ",".join(KERNELS):
+        out["kernels"] = json.load(open(a.out))["kernels"]
     cache = {}
     with tempfile.TemporaryDirectory() as td:
         for label in a.kernels.split(","):
@@ -135,6 +141,8 @@ def main():
                 "valu_elem_per_cell": round(elem / cells, 3),
                 "cycles_per_lane_cell": round(cpc, 3),
                 "peak_gcups": round(SIMDS * CLOCK * 64 / cpc / 1e9, 1),
+                "valu_in_block": valu,
+                "scratch_in_block": sum(v for k, v in cnt.items() if k.startswith("scratch_")),
                 "mix": dict(sorted(((k, v) for k, v in cnt.items() if k.startswith("v_")), key=lambda x: -x[1])),
                 "unpriced_at_slow_rate": unknown}
             print(f"{label:14s} VALU/cell {valu / cells:6.2f}  cycles/lane-cell {cpc:6.2f}  "

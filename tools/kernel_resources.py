@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Register and scratch use of every fill_kernel and banded_fill_kernel instantiation of a translation
-unit, from the compiler's own resource-usage remarks (no GPU needed).
+"""Register and scratch use of every fill_kernel, fill_so2_kernel and banded_fill_kernel instantiation
+of a translation unit, from the compiler's own resource-usage remarks (no GPU needed).
 
     tools/kernel_resources.py seqalib_amd/csrc/sa_fill_sw_score.hip [more units ...] > table.txt
     tools/kernel_resources.py --parse remarks.txt ...      # remarks captured earlier
 
 One line per kernel: algorithm, R, match flavour, ALLOW, KEYED, plan (one workgroup per pair /
 SPLIT), VGPRs, SGPRs, scratch bytes per lane, occupancy (waves per SIMD), LDS bytes.  Exits 1 if any
-kernel uses scratch."""
+kernel uses scratch -- the two-pairs-per-wave fills (fill_so2_kernel: algorithm, R, cell, column table)
+excepted: theirs holds unit-prologue state outside the chunk loop (tools/issue_model.py prices the
+loop)."""
 import re
 import subprocess
 import sys
@@ -18,6 +20,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-devic
 NAME = re.compile(r"Function Name: _ZN2sa11fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
 FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
 BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E")
+SO2 = re.compile(r"Function Name: _ZN2sa15fill_so2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
+CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
 MM = ["eq", "lut", "bits"]
 
@@ -42,6 +46,11 @@ def parse(text):
             cur = {"banded": tuple(int(x) for x in m.groups())}
             rows.append(cur)
             continue
+        m = SO2.search(line)
+        if m:   # the two-pairs-per-wave fills (sa_fill_so2.hip): algorithm, R, FK, TAB
+            cur = {"so2": tuple(int(x) for x in m.groups())}
+            rows.append(cur)
+            continue
         if "Function Name:" in line:
             cur = None
             continue
@@ -58,8 +67,18 @@ def main(argv):
     for f in files:
         rows += parse(open(f).read() if parse_only else remarks(f))
     banded = sorted((r for r in rows if "banded" in r), key=lambda r: r["banded"])
+    so2 = sorted((r for r in rows if "so2" in r), key=lambda r: r["so2"])
     rows = [r for r in rows if "args" in r]
     rows.sort(key=lambda r: r["args"])
+    if so2:
+        print(f"{'so2':<5}{'R':>3} {'cell':<9}{'table':>6}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
+        for r in so2:
+            alg, R, fk, tab = r["so2"]
+            print(f"{ALG[alg]:<5}{R:>3} {CELL[fk]:<9}{'LDS' if tab else 'DPP':>6}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}"
+                  f"{r['ScratchSize']:>8}{r['Occupancy']:>6}{r['LDS']:>7}")
+        print(f"# {len(so2)} two-pairs-per-wave kernels")
+        if not rows and not banded:
+            return 0
     if banded:
         print(f"{'banded':<8}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
         bad_banded = 0
