@@ -26,6 +26,13 @@ public:
     SmithWatermanSA() : BaseType(getDefaultScoring(), nullptr) {}
     SmithWatermanSA(ScoringSystem Scoring, MatchFnTy Match = nullptr) : BaseType(Scoring, Match) {}
 
+    // Extension: substitution scoring (sa_align_batch_matrix).  Once set, getAlignment(s), getScores
+    // and getEndCells score a diagonal move with Fn(Seq1 symbol, Seq2 symbol) instead of the scoring's
+    // match / mismatch; the match function still decides Entry::IsMatchingPair.  A batch may use at
+    // most 64 distinct symbols and scores must fit 16 bits (std::runtime_error otherwise); an empty
+    // function returns to match / mismatch scoring.
+    void setSubstitution(std::function<ScoreSystemType(Ty, Ty)> Fn) { BaseType::setSubstitutionFn(std::move(Fn)); }
+
     virtual AlignedSequence<Ty, Blank> getAlignment(ContainerType& Seq1, ContainerType& Seq2) {
         std::vector<std::pair<ContainerType*, ContainerType*>> one{{&Seq1, &Seq2}};
         return std::move(getAlignments(one)[0]);

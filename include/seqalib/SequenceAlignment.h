@@ -112,9 +112,16 @@ template <typename ContainerType, typename Ty = typename ContainerType::value_ty
 class SequenceAligner {
     ScoringSystem Scoring;
     MatchFnTy Match;
+    std::function<ScoreSystemType(Ty, Ty)> Substitution;
+
+protected:
+    // The DP aligners' setSubstitution(): score diagonal moves with Fn(Seq1 symbol, Seq2 symbol)
+    // instead of the scoring's match / mismatch (an empty function turns it off again).
+    void setSubstitutionFn(std::function<ScoreSystemType(Ty, Ty)> Fn) { Substitution = std::move(Fn); }
 
 public:
     using EntryType = typename AlignedSequence<Ty, Blank>::Entry;
+    const std::function<ScoreSystemType(Ty, Ty)>& getSubstitution() const { return Substitution; }
 
     SequenceAligner(ScoringSystem Scoring, MatchFnTy Match = nullptr) : Scoring(Scoring), Match(Match) {}
     virtual ~SequenceAligner() {}
@@ -211,9 +218,11 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
     PhaseTimer tm;
     size_t cp = kChunkPairs;
     if (const char* e = std::getenv("SEQALIB_LIST_CHUNK_PAIRS")) cp = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
-    const size_t G = band == kNoBand && cp <= P / 2 ? (P + cp - 1) / cp : 1;   // (a banded call is one range)
+    const std::function<ScoreSystemType(Ty, Ty)>* sub = self.getSubstitution() ? &self.getSubstitution() : nullptr;
+    // (a banded call is one range, and so is a matrix call)
+    const size_t G = band == kNoBand && !sub && cp <= P / 2 ? (P + cp - 1) / cp : 1;
     if (G == 1) {
-        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band);
+        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub);
         build_range(0, P);
         tm.lap("AlignedSequence lists");
         return out;
@@ -280,7 +289,8 @@ void run_scores(Aligner& self, const std::vector<std::pair<ContainerType*, Conta
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
     res.clear();
-    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band);
+    const std::function<ScoreSystemType(Ty, Ty)>* sub = self.getSubstitution() ? &self.getSubstitution() : nullptr;
+    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub);
 }
 
 }  // namespace detail

@@ -400,14 +400,40 @@ inline void banded_needs_table(bool overflow) {
         throw std::runtime_error("seqalib: banded calls take batches of at most " + std::to_string(kBandedMaxSymbols) +
                                  " distinct symbols (the per-pair match bitmaps have no banded variant)");
 }
+// setSubstitution(): the dense 256 x 256 int16 table of sa_align_batch_matrix, the caller's score
+// function evaluated once on every pair of symbols the batch uses (its codes index the table).
+constexpr size_t kMatrixMaxSymbols = 64;
+template <typename Ty, typename SubFnTy, bool Direct>
+std::vector<int16_t> build_submat(SymbolCoder<Ty, Direct>& coder, const SubFnTy& sub) {
+    const size_t k = Direct ? 256 : coder.size();
+    size_t used = 0;
+    for (size_t a = 0; a < k; ++a) used += coder.used(a) ? 1 : 0;
+    if (coder.overflow || used > kMatrixMaxSymbols)
+        throw std::runtime_error("seqalib: substitution scoring takes batches of at most " + std::to_string(kMatrixMaxSymbols) +
+                                 " distinct symbols");
+    std::vector<int16_t> tab(65536, 0);
+    for (size_t a = 0; a < k; ++a) {
+        if (!coder.used(a)) continue;
+        for (size_t b = 0; b < k; ++b) {
+            if (!coder.used(b)) continue;
+            const long long v = (long long)sub(coder.value(a), coder.value(b));
+            if (v < INT16_MIN || v > INT16_MAX) throw std::runtime_error("seqalib: substitution scores must fit 16 bits");
+            tab[a * 256 + b] = (int16_t)v;
+        }
+    }
+    return tab;
+}
+
 using ChunkFn = std::function<void(size_t, size_t)>;
 inline void chunk_tramp(void* user, uint32_t p0, uint32_t p1) { (*static_cast<ChunkFn*>(user))(p0, p1); }
 
-template <typename Ty, typename ContainerType, typename MatchFnTy>
+// sub: the aligner's setSubstitution() function, or NULL; with one the batch takes the matrix call
+// (one range, this thread's context, no band; fn then only labels matching pairs).
+template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubFnTy = std::function<int(Ty, Ty)>>
 void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
            std::vector<sa_result>& res, raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off,
-           uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand) {
+           uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand, const SubFnTy* sub = nullptr) {
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -415,6 +441,28 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     std::vector<uint64_t>&o1 = pk.o1, &o2 = pk.o2;
     raw_vector<uint8_t>&s1 = *pk.s1, &s2 = *pk.s2;
     tm.lap("symbol coding");
+    if (sub) {
+        if (band != kNoBand) throw std::runtime_error("seqalib: substitution scoring has no banded call");
+        const std::vector<int16_t> tab = build_submat(coder, *sub);
+        std::vector<uint8_t> mlut;
+        if (has_fn) mlut = build_lut(coder, fn);
+        const uint32_t n = (uint32_t)pairs.size();
+        res.assign(n, sa_result{});
+        const uint64_t cap = s1.size() + s2.size() + n + 1;
+        ops.resize(cap);
+        ops_off.resize(n);
+        for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
+        tm.lap("score table + buffers");
+        check(sa_align_batch_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
+                                    has_fn ? mlut.data() : nullptr, res.data(), ops.data(), cap),
+              "sa_align_batch_matrix");
+        tm.lap("sa_align_batch_matrix (GPU)");
+        if (on_chunk && n) on_chunk(0, n);
+        for (auto& r : res)
+            if (r.flags & SA_FLAG_DIVERGED)
+                throw std::runtime_error("seqalib: the reference traceback does not terminate for this scoring");
+        return;
+    }
     if (band != kNoBand) banded_needs_table(coder.overflow);
     if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
         align_bits<Ty>(algo, sc, fn, has_fn, pairs, res, ops, ops_off);
@@ -461,10 +509,10 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
 // dispatch of align() -- byte symbols, or a symbol table of up to 256 symbols, or match bitmaps
 // above that, or the multi-GPU handle -- without an op buffer anywhere.  res[p]: score and end cell
 // of pair p (start = -1, nops = 0).
-template <typename Ty, typename ContainerType, typename MatchFnTy>
+template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubFnTy = std::function<int(Ty, Ty)>>
 void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
-           long long band = kNoBand) {
+           long long band = kNoBand, const SubFnTy* sub = nullptr) {
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -474,7 +522,16 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     tm.lap("symbol coding");
     const uint32_t n = (uint32_t)pairs.size();
     res.assign(n, sa_result{});
-    if (band != kNoBand) {
+    if (sub) {
+        if (band != kNoBand) throw std::runtime_error("seqalib: substitution scoring has no banded call");
+        const std::vector<int16_t> tab = build_submat(coder, *sub);
+        std::vector<uint8_t> mlut;
+        if (has_fn) mlut = build_lut(coder, fn);
+        check(sa_score_batch_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
+                                    has_fn ? mlut.data() : nullptr, res.data()),
+              "sa_score_batch_matrix");
+        tm.lap("sa_score_batch_matrix (GPU)");
+    } else if (band != kNoBand) {
         banded_needs_table(coder.overflow);
         std::vector<uint8_t> lut;
         if (has_fn) lut = build_lut(coder, fn);

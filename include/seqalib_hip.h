@@ -280,6 +280,53 @@ int sa_score_batch_banded(sa_ctx* ctx, int algo, const sa_scoring* scoring,
 int sa_banded_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs,
                          int* cells_per_lane, int* pairs_per_wave, uint64_t* workspace_bytes_per_pair);
 
+/* Substitution-matrix scoring: the diagonal move of cell (i, j) scores submat[a * 256 + b], a = Seq1
+ * symbol i-1, b = Seq2 symbol j-1, instead of one of the two numbers match / mismatch.
+ *   submat: a dense 256 x 256 int16 table on the host; it need not be symmetric, and only the entries
+ *     of symbols that occur in the batch are read.
+ *   algo: SA_SW, SA_NW, SA_LOCAL_GOTOH, SA_GLOBAL_GOTOH; SA_HIRSCHBERG and SA_MYERS_MILLER return
+ *     SA_ERR_UNSUPPORTED.
+ * Recurrences, borders, tie order, the end-cell rule, traceback order and op codes are sa_align_batch's
+ * with allow_mismatch = 1, the term (match(a, b) ? match : mismatch) replaced by submat[a][b].
+ * scoring->match, mismatch and allow_mismatch are ignored; gap (linear) or gap_open / gap_extend
+ * (affine) are read as in sa_align_batch.  A diagonal op is 'M' when match_lut says the two symbols
+ * match (NULL: byte equality), else 'S'; 'X' never appears.  match_lut labels ops only: it changes
+ * no score.
+ * This is the raw path, like the device API: the LocalGotoh size hack is not applied, so
+ * SA_FLAG_SIZE_HACK never appears; SA_FLAG_DIVERGED keeps its meaning.
+ * The score call follows the score contract above: start = (-1, -1), nops = 0, reserved = 0, no walk,
+ * SA_RECORDS_NONE, traceback_ms == 0.
+ * Arguments, the blocking host-buffer contract, sa_ops_offset and the splitting into launches under
+ * sa_set_workspace_limit are sa_align_batch's / sa_score_batch's.  NULL submat, or any other bad
+ * argument: SA_ERR_ARG.  SA_ERR_UNSUPPORTED, with a message, for
+ *   more than 64 distinct symbols in the batch, both sequence sets counted together;
+ *   a pair with (m + n + 1) * max(|gap terms|, max |S|) >= 2^29, where the gap terms are gap (linear)
+ *     or gap_open and gap_extend (affine) and max |S| runs over the symbol pairs of the batch;
+ *   a sequence of 2^24 symbols or more.
+ *   (These checks are made before the context is looked at, so they give the same status with a NULL
+ *   context; a NULL context with valid arguments: SA_ERR_ARG.)
+ * sa_last_timings works after either call; sa_last_plan_ex reports SA_KERNEL_INT32 with the plan of
+ * a LUT batch of the same shape and SA_RECORDS_FLAGS / SA_RECORDS_NONE.  The T16, score-only and
+ * small-call kernels are never used, and every walk is the one-lane-per-pair kernel, whatever
+ * SEQALIB_T16, SEQALIB_TINY or SEQALIB_TB say. */
+int sa_align_batch_matrix(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                          const uint8_t* seq1, const uint64_t* seq1_off,
+                          const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                          const int16_t* submat, const uint8_t* match_lut,
+                          sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_matrix(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                          const uint8_t* seq1, const uint64_t* seq1_off,
+                          const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                          const int16_t* submat, const uint8_t* match_lut, sa_result* results);
+/* Plan of sa_align_batch_matrix for a batch of npairs pairs up to max_m x max_n with nsym distinct
+ * symbols (host-only query, no device needed): always SA_KERNEL_INT32, with the rows per lane, waves
+ * (0: one single-wave workgroup per band) and per-pair workspace sa_plan_query_ex reports for a batch
+ * that runs the int32 kernel alone (a forced plan of 16 rows per lane runs at most 8 waves).  The
+ * scoring's match / mismatch are not read.  nsym > 64 and lengths >= 2^24: SA_ERR_UNSUPPORTED. */
+int sa_matrix_plan_query(int algo, const sa_scoring* scoring, uint32_t max_m, uint32_t max_n,
+                         uint32_t npairs, int nsym, int* kernel, int* rows_per_lane, int* waves,
+                         uint64_t* workspace_bytes_per_pair);
+
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events
  * recorded on the stream they ran on: total fill-kernel ms, total traceback-kernel ms, and the
  * number of fill launches.  Waits for those events. */

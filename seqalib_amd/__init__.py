@@ -144,6 +144,11 @@ def load_library():
     L.sa_banded_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p]
     L.sa_score_plan_query.argtypes = [C.c_int, C.POINTER(_Scoring), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                       i32p, i32p, i32p, u64p]
+    L.sa_align_batch_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
+                                        vp, vp, C.c_uint64]
+    L.sa_score_batch_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.sa_matrix_plan_query.argtypes = [C.c_int, C.POINTER(_Scoring), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                       i32p, i32p, i32p, u64p]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
     L.sa_last_kernel_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sa_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p, u64p]
@@ -162,6 +167,7 @@ def load_library():
                "sa_score_batch_device", "sa_multi_score_batch", "sa_score_plan_query",
                "sa_last_timings", "sa_last_kernel_timings", "sa_last_plan", "sa_last_plan_ex", "sa_plan_query", "sa_plan_query_ex", "sa_synth_dna", "sa_synth_mutate", "sa_synth_dna_batch",
                "sa_align_batch_banded", "sa_score_batch_banded", "sa_banded_plan_query",
+               "sa_align_batch_matrix", "sa_score_batch_matrix", "sa_matrix_plan_query",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -327,6 +333,59 @@ def _as_bytes(s) -> bytes:
     if isinstance(s, np.ndarray) and s.dtype == np.uint8:
         return s.tobytes()
     raise TypeError("sequences must be str, bytes or uint8 arrays (use the symbol mapping for other types)")
+
+
+class SubstitutionMatrix:
+    """Dense 256 x 256 int16 score table for the matrix calls (sa_align_batch_matrix): table[a, b] is
+    the diagonal term of Seq1 symbol a against Seq2 symbol b.
+
+    alphabet: the symbols (str, bytes or ints 0..255) that index `table`;
+    table: a K x K array-like (table[i][j] = score of alphabet[i] against alphabet[j], not
+           necessarily symmetric), or a dict {(a, b): score} over symbols of the alphabet;
+    default: the score of every pair the table does not give (pairs of a dict that are missing,
+             symbols outside the alphabet); None leaves those at 0."""
+
+    def __init__(self, alphabet, table, default: Optional[int] = None):
+        def sym(x):
+            if isinstance(x, str):
+                x = ord(x)
+            x = int(x)
+            if not 0 <= x <= 255:
+                raise SeqalibError(f"symbol {x} is not a byte")
+            return x
+
+        syms = [sym(x) for x in alphabet]
+        if len(set(syms)) != len(syms):
+            raise SeqalibError("SubstitutionMatrix: the alphabet repeats a symbol")
+        self.alphabet = bytes(syms)
+        full = np.full((256, 256), 0 if default is None else int(default), dtype=np.int64)
+        if isinstance(table, dict):
+            for (a, b), v in table.items():
+                a, b = sym(a), sym(b)
+                if a not in syms or b not in syms:
+                    raise SeqalibError("SubstitutionMatrix: table entry outside the alphabet")
+                full[a, b] = int(v)
+        else:
+            t = np.asarray(table, dtype=np.int64)
+            if t.shape != (len(syms), len(syms)):
+                raise SeqalibError(f"SubstitutionMatrix: table must be {len(syms)} x {len(syms)}")
+            full[np.ix_(syms, syms)] = t
+        if full.min() < -32768 or full.max() > 32767:
+            raise SeqalibError("SubstitutionMatrix: scores must fit int16")
+        self.table = np.ascontiguousarray(full, dtype=np.int16)
+
+    def score(self, a, b) -> int:
+        a = ord(a) if isinstance(a, str) else int(a)
+        b = ord(b) if isinstance(b, str) else int(b)
+        return int(self.table[a, b])
+
+
+def _submat_arg(matrix) -> np.ndarray:
+    t = matrix.table if isinstance(matrix, SubstitutionMatrix) else matrix
+    t = np.ascontiguousarray(t, dtype=np.int16)
+    if t.size != 65536:
+        raise SeqalibError("substitution matrix must be a SubstitutionMatrix or a 256 x 256 int16 table")
+    return t.reshape(65536)
 
 
 def pack_pairs(pairs: Sequence[Tuple[object, object]]):
@@ -510,6 +569,69 @@ class Engine:
         """score() through the banded call."""
         s1, off1, s2, off2 = pack_pairs(pairs)
         return self._score_results(self.score_banded_packed(algo, scoring, s1, off1, s2, off2, band, lut))
+
+    def align_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                            s2: np.ndarray, off2: np.ndarray, matrix, lut: Optional[np.ndarray] = None):
+        """Substitution-matrix host-buffer batch (sa_align_batch_matrix): the diagonal term is
+        matrix[a, b] (a SubstitutionMatrix or a 256 x 256 int16 table); only the gap terms of
+        `scoring` are read; `lut` labels diagonal ops 'M' / 'S'.  Returns (results, ops) as align_packed."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        tab = _submat_arg(matrix)
+        ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        ops = np.zeros(ops_cap, dtype=np.uint8)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_align_batch_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                          npairs, _ptr(tab), lut_p, _ptr(res), _ptr(ops), ops_cap)
+        self._check(rc, "sa_align_batch_matrix")
+        return res[:npairs], ops
+
+    def score_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                            s2: np.ndarray, off2: np.ndarray, matrix, lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Substitution-matrix score batch (sa_score_batch_matrix): the results array (start = -1, nops = 0)."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        tab = _submat_arg(matrix)
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_score_batch_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                          npairs, _ptr(tab), lut_p, _ptr(res))
+        self._check(rc, "sa_score_batch_matrix")
+        return res[:npairs]
+
+    def align_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
+                     lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the matrix call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        res, ops = self.align_matrix_packed(algo, scoring, s1, off1, s2, off2, matrix, lut)
+        out = []
+        for p in range(len(pairs)):
+            o = int(off1[p] + off2[p]) + p
+            r = res[p]
+            out.append(PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]),
+                                  int(r["start_j"]), int(r["flags"]), ops[o:o + int(r["nops"])].tobytes()))
+        return out
+
+    def score_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
+                     lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the matrix call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_matrix_packed(algo, scoring, s1, off1, s2, off2, matrix, lut))
 
     def align_bits(self, algo: int, scoring: ScoringSystem, off1: np.ndarray, off2: np.ndarray, bits: np.ndarray,
                    bits_off: np.ndarray):
@@ -705,6 +827,19 @@ def banded_plan_query(algo: int, max_m: int, max_n: int, band: int, npairs: int 
     return R.value, ppw.value, ws.value
 
 
+def matrix_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 20):
+    """(kernel, R, W, workspace bytes per pair) of sa_align_batch_matrix for a batch of this shape with
+    nsym distinct symbols (sa_matrix_plan_query; no GPU needed)."""
+    L = load_library()
+    k, r, w, ws = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+    sc = scoring._c()
+    rc = L.sa_matrix_plan_query(algo, C.byref(sc), max_m, max_n, npairs, nsym, C.byref(k), C.byref(r), C.byref(w),
+                                C.byref(ws))
+    if rc != 0:
+        raise SeqalibError(f"sa_matrix_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
+    return k.value, r.value, w.value, ws.value
+
+
 def score_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 4):
     """plan_query_ex for a host score call (sa_score_plan_query): with nsym > 4 the record-free int32
     fill, whose workspace per pair holds no direction records.  SA_MYERS_MILLER raises."""
@@ -763,9 +898,15 @@ def _engine(device: int = 0) -> Engine:
 class _Aligner:
     ALGO = SA_SW
 
-    def __init__(self, scoring: Optional[ScoringSystem] = None, match=None, device: int = 0, blank="-"):
+    def __init__(self, scoring: Optional[ScoringSystem] = None, match=None, device: int = 0, blank="-", matrix=None):
+        """matrix: a SubstitutionMatrix (or 256 x 256 int16 table); the aligner then scores diagonal
+        moves with it through the matrix calls (the scoring's gap terms still apply, `match` only
+        labels matching pairs).  SmithWatermanSA, NeedlemanWunschSA, LocalGotohSA and GlobalGotohSA."""
         self.scoring = scoring if scoring is not None else self.getDefaultScoring()
         self.match_fn = match
+        if matrix is not None and self.ALGO in (SA_HIRSCHBERG, SA_MYERS_MILLER):
+            raise SeqalibError(f"{type(self).__name__} does not take a substitution matrix")
+        self.matrix = None if matrix is None else _submat_arg(matrix)
         self.device = device
         self.blank = blank
         self.last: Optional[PairResult] = None
@@ -791,7 +932,11 @@ class _Aligner:
         """band: half-width of the banded call (NeedlemanWunschSA, HirschbergSA = NW, SmithWatermanSA;
         the other aligners raise SeqalibError); None: the unbanded path."""
         eng = _engine(self.device)
-        if band is None:
+        if self.matrix is not None:
+            if band is not None:
+                raise SeqalibError("a substitution matrix and band= cannot be combined")
+            res = eng.align_matrix(self.ALGO, self.scoring, pairs, self.matrix, self._lut(pairs))
+        elif band is None:
             res = eng.align(self.ALGO, self.scoring, pairs, self._lut(pairs))
         else:
             res = eng.align_banded(self.ALGO, self.scoring, pairs, band, self._lut(pairs))
@@ -813,7 +958,11 @@ class _Aligner:
         return None if self.last is None else self.last.score
 
     def _score_results(self, pairs, band: Optional[int] = None) -> List[PairResult]:
-        if band is None:
+        if self.matrix is not None:
+            if band is not None:
+                raise SeqalibError("a substitution matrix and band= cannot be combined")
+            res = _engine(self.device).score_matrix(self.ALGO, self.scoring, pairs, self.matrix, self._lut(pairs))
+        elif band is None:
             res = _engine(self.device).score(self.ALGO, self.scoring, pairs, self._lut(pairs))
         else:
             res = _engine(self.device).score_banded(self.ALGO, self.scoring, pairs, band, self._lut(pairs))

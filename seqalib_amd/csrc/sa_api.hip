@@ -739,6 +739,12 @@ int build_variants(int algo, uint32_t max_m, uint32_t max_n, uint32_t npairs, bo
     return nv;
 }
 
+// The kMatchSub kernels at R = 16 are built for 8 waves (fill_kernel_threads, sa_fill_impl.h).
+void cap_sub_waves(Variant (&vars)[3], int count) {
+    for (int k = 0; k < count; ++k)
+        if (vars[k].pl.R >= 16 && vars[k].pl.W > 8) vars[k].pl.W = 8;
+}
+
 // The batch alphabet decided on the host (host API calls whose sequences are small enough to scan
 // here, align_host): the same decision and profile as decide_t16 (sa_alphabet.hip) -- <= 4
 // distinct bytes, padded with absent byte values, prof[c] byte c' = 4s + 3 (8s + 6 affine) with
@@ -809,7 +815,13 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                uint32_t max_n, const uint32_t* d_lutbits, sa_result* d_res, uint8_t* d_ops,
                hipStream_t stream, bool pipe = false, const uint32_t* d_mbits = nullptr,
                const uint64_t* d_mbits_off = nullptr, const HostSeqs* hs = nullptr, bool notb = false,
-               bool many_syms = false) {
+               bool many_syms = false, const int16_t* d_submat = nullptr, uint32_t sub_k = 0) {
+    // d_submat (a matrix call, matrix_batch): the sequences hold symbol codes, sc->match / mismatch are
+    // the table's largest positive and smallest negative entry (0 if none: what keyed_ok bounds a
+    // local score with), d_lutbits labels the ops over codes.  The kMatchSub int32 variant runs alone
+    // (many_syms), on whatever plan the int32 planner picks, SPLIT included; every walk is the
+    // one-lane-per-pair kernel (launch_traceback_sub), whatever $SEQALIB_TB says, and the segmented
+    // traceback is off.
     // notb: a score call -- the fills, the end-cell replays and score_finish on the fill stream,
     // nothing on the traceback stream (d_ops is NULL).  many_syms: the caller knows the batch holds
     // more than 4 distinct symbols, so T16 is no candidate and the int32 variant runs alone.
@@ -819,6 +831,8 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
     const bool keyed = keyed_ok(algo, sc, max_m, max_n);
     const bool allow = sc->allow_mismatch != 0;
     const bool bits = d_mbits != nullptr;   // generic-Ty path: per-pair match bitmaps
+    const bool sub = d_submat != nullptr;
+    if (sub && (bits || !d_lutbits || !many_syms || !allow || pipe)) return fail(c, SA_ERR_ARG, "internal: matrix call");
     const bool lut = !bits && d_lutbits != nullptr;
     const T16Mode tm = (bits || many_syms) ? T16Mode{} : t16_candidate(algo, sc, max_m, max_n, npairs);
     const bool t16 = tm.ok;
@@ -896,6 +910,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
     Variant vars[3];
     bool has_fb = false;
     const int nv = build_variants(algo, max_m, max_n, npairs, t16, vars, &has_fb, only, notb);
+    if (sub) cap_sub_waves(vars, nv + (has_fb ? 1 : 0));
     if (const char* e = getenv("SEQALIB_SPLIT_FALLBACK")) has_fb = has_fb && e[0] != '0';   // tests only
     c->nvar = nv;
     uint64_t slot_bytes = 0, sp_bands = 0;
@@ -948,7 +963,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
     const uint64_t sp_gran = any_split ? per_launch * sp_bands * std::max<uint32_t>(max_n, 1) * aff2 : 0;
     const uint64_t sp_vblk = (256 + sp_gran * 8 + 255) & ~(uint64_t)255;
     const uint64_t sp_part = (uint64_t)nv * sp_vblk;
-    const int seg_mode = any_split && !notb && tb_wave((uint32_t)per_launch) ? tb_seg_mode() : 0;
+    const int seg_mode = any_split && !notb && !sub && tb_wave((uint32_t)per_launch) ? tb_seg_mode() : 0;
     // tests only: SEQALIB_SPLIT_WAIT_TICKS shortens the SPLIT bands' bounded wait (forces timeouts
     // and the fallback); SEQALIB_SEG_INJECT=1 overwrites the segmented traceback's exit records
     // between its two kernels (forces its consistency guards and the serial re-walk)
@@ -1120,6 +1135,8 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             fv.so = v.so;
             fv.so2 = v.so2;
             fv.norec = v.norec;
+            fv.sub = sub;
+            fp.submat = d_submat; fp.sub_k = sub_k;
             return fv;
         };
         // Pipelined calls: the int32 variant of a T16 batch (it re-runs only the pairs the T16 fill
@@ -1155,6 +1172,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             // the int32 re-run walked first (tb_on_fill): it leaves kFlagRedo, the T16 walk clears it
             tp.keep_redo = tb_on_fill && k == 1 ? 1 : 0;
             tp.clear_redo = tb_on_fill && k == 0 ? 1 : 0;
+            tp.submat = d_submat; tp.sub_k = sub_k;
 #ifdef SA_R5_CONTROL
             tp.keep_redo = tp.clear_redo = 0;   // (round 5: the int32 walk cleared kFlagRedo)
 #endif
@@ -1176,7 +1194,8 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             const bool units = v.so && !is_affine(algo);
             const uint32_t grid = pl.split ? (uint32_t)(cnt * sp_bands)
                                 : units ? (v.so2 ? (cnt + 1) / 2 : cnt) * pl.g.bands * v.segs : cnt;
-            hipError_t e = v.so2 ? launch_fill_so2(algo, pl.R, fp, grid, sf)
+            hipError_t e = sub ? launch_fill_sub(algo, fv, fp, grid, sf)
+                         : v.so2 ? launch_fill_so2(algo, pl.R, fp, grid, sf)
                          : v.norec ? launch_fill_score(algo, fv, fp, grid, sf) : launch_fill(algo, fv, fp, grid, sf);
             if (e != hipSuccess) return hip_fail(c, e, "fill kernel launch");
             if (kev) SA_HIP(c, hipEventRecord(kev[2 * k + 1], sf));
@@ -1242,7 +1261,7 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             if (has_fb) {
                 if (vars[nv].pl.split) return fail(c, SA_ERR_UNSUPPORTED, "internal: SPLIT fallback plan");
                 const FillVariant fv = make_fp(nv);
-                hipError_t e = launch_fill_score(algo, fv, fps[nv], cnt, sf);
+                hipError_t e = sub ? launch_fill_sub(algo, fv, fps[nv], cnt, sf) : launch_fill_score(algo, fv, fps[nv], cnt, sf);
                 if (e != hipSuccess) return hip_fail(c, e, "fallback fill kernel launch");
             }
             hipError_t e = launch_score_finish(d_res, (uint32_t)base, cnt, sf);
@@ -1267,7 +1286,8 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
                 if (e != hipSuccess) return hip_fail(c, e, "segmented traceback kernel launch");
                 ++c->tb_kernels;
             }
-            hipError_t e = v.so ? launch_traceback_so(algo, v.pl.R, tp, stb)
+            hipError_t e = sub ? launch_traceback_sub(algo, v.pl.R, tp, stb)
+                         : v.so ? launch_traceback_so(algo, v.pl.R, tp, stb)
                          : tb_wave(cnt) ? launch_traceback_wave(algo, v.pl.R, lut, tp, stb)
                                         : launch_traceback(algo, v.pl.R, lut, tp, stb);
             if (e != hipSuccess) return hip_fail(c, e, "traceback kernel launch");
@@ -1279,10 +1299,11 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
             // pairs it re-runs): fill + traceback of exactly the pairs flagged SA_FLAG_TIMEOUT,
             // launches that return at once when there is none
             const FillVariant fv = make_fp(nv);
-            hipError_t e = launch_fill(algo, fv, fps[nv], cnt, stb);
+            hipError_t e = sub ? launch_fill_sub(algo, fv, fps[nv], cnt, stb) : launch_fill(algo, fv, fps[nv], cnt, stb);
             if (e != hipSuccess) return hip_fail(c, e, "fallback fill kernel launch");
             const TbParams tp = make_tp(nv);
-            e = tb_wave(cnt) ? launch_traceback_wave(algo, vars[nv].pl.R, lut, tp, stb)
+            e = sub ? launch_traceback_sub(algo, vars[nv].pl.R, tp, stb)
+              : tb_wave(cnt) ? launch_traceback_wave(algo, vars[nv].pl.R, lut, tp, stb)
                              : launch_traceback(algo, vars[nv].pl.R, lut, tp, stb);
             if (e != hipSuccess) return hip_fail(c, e, "fallback traceback kernel launch");
             c->tb_kernels += 2;
@@ -2614,6 +2635,179 @@ int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t
     uint64_t ws = 0;
     for (int k = 0; k < nv + (has_fb ? 1 : 0); ++k) ws = std::max(ws, vars[k].slot_bytes);
     if (ws_bytes_per_pair) *ws_bytes_per_pair = ws;
+    return SA_OK;
+}
+
+// ------------------------------------------------------------------------- matrix calls
+// sa_align_batch_matrix / sa_score_batch_matrix (kernels: the kMatchSub fills, sa_fill_*_sub*.hip, and
+// the SUB walk of sa_traceback.hip).  The host scans the batch's symbols, gives them codes 0..K-1 in
+// byte order, recodes both sequence sets while it copies them to the pinned upload staging, and packs
+// the used K x K corner of the caller's table densely; the label table (match_lut or equality) becomes
+// a bit table over codes.  run_device then runs the int32 planner's plan with that table.
+
+// Algorithm, scoring and table checks shared with sa_matrix_plan_query (c may be NULL).
+static int matrix_prologue(sa_ctx* c, int algo, const sa_scoring* sc) {
+    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
+    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
+    if (algo == SA_HIRSCHBERG || algo == SA_MYERS_MILLER)
+        return fail(c, SA_ERR_UNSUPPORTED, "matrix calls support SA_SW, SA_NW, SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH only");
+    return SA_OK;
+}
+
+static int matrix_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                        const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
+                        const uint8_t* lut, sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
+    // (the checks that need no context come first, so they answer without a device too)
+    int rc = matrix_prologue(c, algo, sc);
+    if (rc) return rc;
+    if (!submat) return fail(c, SA_ERR_ARG, "submat is NULL");
+    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
+    if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
+    if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
+    for (uint32_t p = 0; p < npairs; ++p)
+        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
+    const uint64_t t1 = off1[npairs], t2 = off2[npairs];
+
+    // the batch's symbols, both sides together: codes in byte order
+    bool seen[256] = {};
+    for (uint64_t k = 0; k < t1; ++k) seen[seq1[k]] = true;
+    for (uint64_t k = 0; k < t2; ++k) seen[seq2[k]] = true;
+    uint8_t code[256] = {};
+    int syms[kSubMaxSyms];
+    int K = 0;
+    for (int b = 0; b < 256; ++b)
+        if (seen[b]) {
+            if (K == kSubMaxSyms)
+                return fail(c, SA_ERR_UNSUPPORTED, "matrix calls take batches of at most " + std::to_string(kSubMaxSyms) +
+                                                       " distinct symbols (both sequence sets together)");
+            code[b] = (uint8_t)K;
+            syms[K++] = b;
+        }
+    if (K == 0) syms[K++] = 0;   // (no symbol at all: a one-entry table nobody reads)
+    // the used corner, its extremes, and the score bound: with every step of a path adding at most
+    // `big` in magnitude (a gap opening at most twice that), (m + n + 1) * big < 2^29 keeps every
+    // cell -- and the Gotoh borders of -10000 plus such a path -- inside int32
+    std::vector<int16_t> tab(kSubMaxSyms * kSubMaxSyms, 0);
+    int32_t smax = 0, smin = 0;
+    for (int a = 0; a < K; ++a)
+        for (int b = 0; b < K; ++b) {
+            const int16_t s = submat[syms[a] * 256 + syms[b]];
+            tab[a * K + b] = s;
+            smax = std::max<int32_t>(smax, s);
+            smin = std::min<int32_t>(smin, s);
+        }
+    auto ab = [](int32_t x) { return (int64_t)(x < 0 ? -(int64_t)x : x); };
+    const int64_t gapbig = is_affine(algo) ? std::max(ab(sc->gap_open), ab(sc->gap_extend)) : ab(sc->gap);
+    const int64_t big = std::max(gapbig, std::max<int64_t>(smax, -(int64_t)smin));
+    uint32_t max_m = 0, max_n = 0;
+    for (uint32_t p = 0; p < npairs; ++p) {
+        const uint64_t m = off1[p + 1] - off1[p], n = off2[p + 1] - off2[p];
+        if (m >= (1u << 24) || n >= (1u << 24)) return fail(c, SA_ERR_UNSUPPORTED, "sequence lengths must be < 2^24");
+        if ((int64_t)(m + n + 1) * big >= (int64_t)kBandScoreLimit)
+            return fail(c, SA_ERR_UNSUPPORTED, "matrix calls need (m + n + 1) * max(|gap terms|, max |S|) < 2^29 for every pair");
+        max_m = std::max(max_m, (uint32_t)m);
+        max_n = std::max(max_n, (uint32_t)n);
+    }
+    if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
+    const uint64_t ops_total = notb ? 0 : t1 + t2 + npairs;
+    if (ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer needs " + std::to_string(ops_total) + " bytes");
+    if (!npairs) return SA_OK;
+    SA_HIP(c, hipSetDevice(c->device));
+    if ((rc = order_after_last(c, c->stream))) return rc;
+
+    // what run_device's host decisions read of the scoring: the diagonal term's extremes (keyed_ok
+    // bounds a local score by match * min(m, n), and by the absolute values when a gap term is positive)
+    sa_scoring sc2 = *sc;
+    sc2.match = smax;
+    sc2.mismatch = smin;
+    sc2.allow_mismatch = 1;
+
+    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
+    const uint64_t b_s1 = al(t1 + 1), b_s2 = al(t2 + 1), b_o = al(8ull * (npairs + 1)), b_res = al(sizeof(sa_result) * (uint64_t)npairs);
+    const uint64_t b_ops = al(ops_total + 1), b_bits = al(8192), b_tab = al(2ull * kSubMaxSyms * kSubMaxSyms);
+    if ((rc = ensure_io(c, b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_bits + b_tab))) return rc;
+    uint8_t* q = c->io;
+    uint8_t* const d1 = q; q += b_s1;
+    uint8_t* const d2 = q; q += b_s2;
+    uint64_t* const do1 = reinterpret_cast<uint64_t*>(q); q += b_o;
+    uint64_t* const do2 = reinterpret_cast<uint64_t*>(q); q += b_o;
+    sa_result* const dres = reinterpret_cast<sa_result*>(q); q += b_res;
+    uint8_t* const dops = q; q += b_ops;
+    uint32_t* const dbits = reinterpret_cast<uint32_t*>(q); q += b_bits;
+    int16_t* const dtab = reinterpret_cast<int16_t*>(q);
+
+    // pinned staging: [Seq1 codes][Seq2 codes][label bits over codes][table]
+    SA_HIP(c, c->stage.alloc(b_s1 + b_s2 + b_bits + b_tab));
+    uint8_t* const h1 = c->stage.data();
+    uint8_t* const h2 = h1 + b_s1;
+    uint32_t* const hbits = reinterpret_cast<uint32_t*>(h2 + b_s2);
+    int16_t* const htab = reinterpret_cast<int16_t*>(h2 + b_s2 + b_bits);
+    par_for(t1, 1u << 20, [&](uint64_t lo, uint64_t hi) { for (uint64_t k = lo; k < hi; ++k) h1[k] = code[seq1[k]]; });
+    par_for(t2, 1u << 20, [&](uint64_t lo, uint64_t hi) { for (uint64_t k = lo; k < hi; ++k) h2[k] = code[seq2[k]]; });
+    memset(hbits, 0, 8192);
+    for (int a = 0; a < K; ++a)
+        for (int b = 0; b < K; ++b)
+            if (lut ? lut[syms[a] * 256 + syms[b]] != 0 : a == b) hbits[a * 8 + b / 32] |= 1u << (b % 32);
+    memcpy(htab, tab.data(), 2ull * kSubMaxSyms * kSubMaxSyms);
+    hipStream_t st = c->stream;
+    if (t1) SA_HIP(c, hipMemcpyAsync(d1, h1, t1, hipMemcpyHostToDevice, st));
+    if (t2) SA_HIP(c, hipMemcpyAsync(d2, h2, t2, hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(dbits, hbits, 8192 + b_tab, hipMemcpyHostToDevice, st));   // (bits and table: adjacent both sides)
+    SA_HIP(c, hipMemcpyAsync(do1, off1, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(do2, off2, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
+
+    rc = run_device(c, algo, &sc2, d1, do1, d2, do2, npairs, max_m, max_n, dbits, dres, notb ? nullptr : dops, st, false,
+                    nullptr, nullptr, nullptr, notb, true, dtab, (uint32_t)K);
+    if (rc) return rc;
+    c->host_sel = -1;
+
+    SA_HIP(c, c->ostage.alloc(b_res + ops_total));
+    sa_result* const sres = reinterpret_cast<sa_result*>(c->ostage.data());
+    uint8_t* const sops = c->ostage.data() + b_res;
+    SA_HIP(c, hipMemcpyAsync(sres, dres, sizeof(sa_result) * (uint64_t)npairs, hipMemcpyDeviceToHost, st));
+    if (!notb && ops_total) SA_HIP(c, hipMemcpyAsync(sops, dops, ops_total, hipMemcpyDeviceToHost, st));
+    if ((rc = mark_last(c, st))) return rc;
+    SA_HIP(c, hipStreamSynchronize(st));
+    memcpy(results, sres, sizeof(sa_result) * (uint64_t)npairs);
+    for (uint32_t p = 0; p < npairs && !notb; ++p) {
+        const uint64_t o = off1[p] + off2[p] + p;
+        memcpy(ops + o, sops + o, results[p].nops);
+    }
+    return SA_OK;
+}
+
+int sa_align_batch_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                          const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
+                          const uint8_t* match_lut, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    return matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, results, ops, ops_cap, false);
+}
+
+int sa_score_batch_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                          const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
+                          const uint8_t* match_lut, sa_result* results) {
+    return matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, results, nullptr, 0, true);
+}
+
+int sa_matrix_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,
+                         int* kernel, int* rows_per_lane, int* waves, uint64_t* workspace_bytes_per_pair) {
+    int rc = matrix_prologue(nullptr, algo, sc);
+    if (rc) return rc;
+    if (nsym < 0) return fail(nullptr, SA_ERR_ARG, "nsym is negative");
+    if (nsym > kSubMaxSyms)
+        return fail(nullptr, SA_ERR_UNSUPPORTED, "matrix calls take batches of at most " + std::to_string(kSubMaxSyms) + " distinct symbols");
+    if (max_m >= (1u << 24) || max_n >= (1u << 24)) return fail(nullptr, SA_ERR_UNSUPPORTED, "sequence lengths must be < 2^24");
+    // the align call's variants: the int32 kernel alone whatever the scoring and the alphabet
+    Variant vars[3];
+    bool has_fb = false;
+    const int nv = build_variants(algo, max_m, max_n, npairs, false, vars, &has_fb);
+    cap_sub_waves(vars, nv + (has_fb ? 1 : 0));
+    const Variant& v = vars[0];
+    if (kernel) *kernel = v.kernel;
+    if (rows_per_lane) *rows_per_lane = v.pl.R;
+    if (waves) *waves = v.pl.split ? 0 : v.pl.W;
+    uint64_t ws = 0;
+    for (int k = 0; k < nv + (has_fb ? 1 : 0); ++k) ws = std::max(ws, vars[k].slot_bytes);
+    if (workspace_bytes_per_pair) *workspace_bytes_per_pair = ws;
     return SA_OK;
 }
 

@@ -120,8 +120,12 @@ constexpr int fill_max_threads() { return (R >= 32 || (WIDE && R >= 16)) ? 256 :
 // local-mode cells (a, H, best score and column per row) spill 20 - 256 bytes per lane, as the
 // recording kernels do (profiles/score_fill_resources.txt); make_variant (sa_api.hip) caps W.
 constexpr int kNorecWideThreads = 512;
-template <int R, bool WIDE, bool NOREC, int MM>
+// The kMatchSub kernels, recording ones included, take 8 waves at R = 16 as well (the recording LUT
+// kernels spill 44 - 328 bytes per lane there), and their SPLIT instantiations -- always launched as
+// 3 waves -- 4: none of them uses scratch (tools/kernel_resources.py; run_device caps W).
+template <int R, bool WIDE, bool NOREC, int MM, bool SPLIT = false>
 constexpr int fill_kernel_threads() {
+    if (MM == kMatchSub) return SPLIT ? 256 : R >= 16 ? kNorecWideThreads : fill_max_threads<R, WIDE>();
     return (NOREC && (R >= 16 || (R >= 8 && MM == kMatchBits))) ? kNorecWideThreads : fill_max_threads<R, WIDE>();
 }
 
@@ -246,6 +250,12 @@ template <int ALG, int R, int MM, bool ALLOW, bool KEYED, bool T16, bool CMAX, b
 __device__ __forceinline__ void fill_body(const FillParams& P) {
     constexpr bool LUT = MM == kMatchLut;
     constexpr bool BITS = MM == kMatchBits;
+    // SUB (the matrix calls): a[r] holds the table row base code(a) * K, the column symbol is a code,
+    // and the diagonal term is the int16 at s_sub[a[r] + sym] -- dense rows (stride K), so the K^2
+    // entries a wave gathers spread over all 32 banks of a 16-bit LDS read whatever K is (a stride of
+    // 64 would put a 20-letter table on 20 of them)
+    constexpr bool SUB = MM == kMatchSub;
+    static_assert(!SUB || (ALLOW && !T16), "SUB: the int32 cell with allow-mismatch");
     constexpr bool AFF = ALG >= SA_LOCAL_GOTOH;
     constexpr int kHandGran = hand_gran<AFF>();   // SPLIT hand-off granule (steps)
     constexpr bool LOCAL = (ALG == SA_SW || ALG == SA_LOCAL_GOTOH);
@@ -430,8 +440,9 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
             }
         }
     }
-    const LdsLayout lay = lds_layout(LUT, AFF, W, P.stage_seq2 ? P.max_n : 0);
+    const LdsLayout lay = lds_layout(LUT || SUB, AFF, W, P.stage_seq2 ? P.max_n : 0);
     uint32_t* const s_lut = smem;
+    const int16_t* const s_sub = reinterpret_cast<const int16_t*>(smem);   // SUB: in the bit table's 8 KiB
     int32_t* const s_ring = reinterpret_cast<int32_t*>(smem + lay.ring_off / 4);
     uint8_t* const s_seq2 = reinterpret_cast<uint8_t*>(smem) + lay.seq_off;
     // LDS-fed steps: a chunk's lane-0 inputs and column symbols are read per step as LDS
@@ -444,6 +455,11 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
     const uint8_t* s2 = P.seq2 + o2;
     if constexpr (LUT) {
         for (int k = threadIdx.x; k < 2048; k += blockDim.x) s_lut[k] = P.lutbits[k];
+    }
+    if constexpr (SUB) {   // K <= kSubMaxSyms: at most 2048 words (the host pads the table to a whole word)
+        const uint32_t* const tw = reinterpret_cast<const uint32_t*>(P.submat);
+        const int words = (int)min((P.sub_k * P.sub_k + 1u) / 2u, 2048u);
+        for (int k = threadIdx.x; k < words; k += blockDim.x) s_lut[k] = tw[k];
     }
     if (P.stage_seq2) {
         // (BU: the columns of this unit's chunks and the 64 before them)
@@ -983,11 +999,12 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
 #undef SA_T16_PW
                     Hc = Hp[r];
                 } else {
-                bool v;
+                bool v = false;
                 if constexpr (BITS) v = (mwin[r] >> q) & 1u;
-                else v = match_bit<LUT>(s_lut, a[r], sym);
+                else if constexpr (!SUB) v = match_bit<LUT>(s_lut, a[r], sym);
                 int D;
-                if constexpr (ALLOW) D = hd + (v ? MA : MI);
+                if constexpr (SUB) D = hd + (int)s_sub[a[r] + sym];
+                else if constexpr (ALLOW) D = hd + (v ? MA : MI);
                 else D = v ? hd + MA : INT_MIN;
                 if constexpr (BPC > FBITS && !NOREC) rw <<= BPC - FBITS;   // record padding (R <= 2)
                 if constexpr (!AFF) {
@@ -1286,6 +1303,7 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
                         // below the matrix maximum, so they never win the lane's chunk maximum)
                         if constexpr (SO) a[r] = row < m ? (int)so_profile<AFF>(P.prof[t16_code8(symp, s1[row]) >> 3]) : (CMAX ? (int)0x80808080u : 0);
                         else if constexpr (T16) a[r] = row < m ? (int)P.prof[t16_code8(symp, s1[row]) >> 3] : (CMAX ? (int)0x80808080u : 0);
+                        else if constexpr (SUB) a[r] = row < m ? (int)((uint32_t)s1[row] * P.sub_k) : 0;
                         else a[r] = row < m ? (int)s1[row] : 0;
                         const int i = row + 1;
                         if constexpr (ALG == SA_NW) Hp[r] = SC * (i * G - P.t16_delta);
@@ -1665,7 +1683,7 @@ __device__ __forceinline__ void fill_body(const FillParams& P) {
 
 template <int ALG, int R, int MM, bool ALLOW, bool KEYED, bool T16, bool CMAX, bool SPLIT, bool SO = false,
           bool NOREC = false>
-__global__ __launch_bounds__((fill_kernel_threads<R, (T16 && ALG >= SA_LOCAL_GOTOH), NOREC, MM>())) void fill_kernel(FillParams P) {
+__global__ __launch_bounds__((fill_kernel_threads<R, (T16 && ALG >= SA_LOCAL_GOTOH), NOREC, MM, SPLIT>())) void fill_kernel(FillParams P) {
     fill_body<ALG, R, MM, ALLOW, KEYED, T16, CMAX, SPLIT, SO, NOREC>(P);
 }
 // The score-only kernel (one wave per workgroup): 4 waves per SIMD.  Its cell needs no record
@@ -1842,6 +1860,42 @@ hipError_t launch_fill_int32(const FillVariant& v, const FillParams& p, uint32_t
 #undef SA_LAUNCH_S
 #undef SA_LAUNCH_K
 #undef SA_LAUNCH
+    return hipErrorInvalidValue;
+}
+
+// The kMatchSub kernels of one algorithm (sa_fill_*_sub.hip; NOREC: sa_fill_*_sub_score.hip): every
+// plan the int32 planner can pick -- R = 4, 8, 16 (SPLIT up to 8) and the SPLIT-only R = 1, 2.
+template <int ALG, bool NOREC>
+hipError_t launch_fill_sub_alg(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream) {
+    constexpr bool LOCAL = (ALG == SA_SW || ALG == SA_LOCAL_GOTOH);
+    const int R = v.R;
+    if (!v.sub || v.t16 || v.cmax || v.so || v.norec != NOREC || !p.submat || p.sub_k < 1 || p.sub_k > (uint32_t)kSubMaxSyms)
+        return hipErrorInvalidValue;
+    const bool keyed = LOCAL && v.keyed;
+    const bool split = v.split;
+    const dim3 block(kWave * (split ? 3 : p.waves));
+    if (R >= 16 && (int)block.x > kNorecWideThreads) return hipErrorInvalidConfiguration;
+    const size_t lds = lds_layout(true, is_affine(ALG), p.waves, p.stage_seq2 ? p.max_n : 0).total;
+    if (lds > kMaxLds) return hipErrorInvalidConfiguration;
+    if (split && (p.waves != 1 || (R != 1 && R != 2 && R != 4 && R != 8))) return hipErrorInvalidConfiguration;
+#define SA_LAUNCH_SUB(RR, KK, SP)                                                                  \
+    if (R == RR && keyed == KK && split == SP) {                                                   \
+        hipLaunchKernelGGL((fill_kernel<ALG, RR, kMatchSub, true, KK, false, false, SP, false, NOREC>), dim3(grid), block, \
+                           lds, stream, p);                                                        \
+        return hipGetLastError();                                                                  \
+    }
+#define SA_LAUNCH_SUB_K(RR, SP) \
+    SA_LAUNCH_SUB(RR, false, SP) \
+    if constexpr (LOCAL) { SA_LAUNCH_SUB(RR, true, SP) }
+    SA_LAUNCH_SUB_K(4, false)
+    SA_LAUNCH_SUB_K(8, false)
+    SA_LAUNCH_SUB_K(16, false)
+    SA_LAUNCH_SUB_K(1, true)
+    SA_LAUNCH_SUB_K(2, true)
+    SA_LAUNCH_SUB_K(4, true)
+    SA_LAUNCH_SUB_K(8, true)
+#undef SA_LAUNCH_SUB_K
+#undef SA_LAUNCH_SUB
     return hipErrorInvalidValue;
 }
 

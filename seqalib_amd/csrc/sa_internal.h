@@ -10,6 +10,12 @@ namespace sa {
 
 // How the fill decides match(Seq1[i-1], Seq2[j-1]) (sa_fill_impl.h).
 constexpr int kMatchEq = 0, kMatchLut = 1, kMatchBits = 2;
+// kMatchSub (the matrix calls, sa_align_batch_matrix): the diagonal term is a table entry
+// S[code(a)][code(b)] read from LDS, not one of two numbers.  The host recodes both sequence sets
+// to the batch's K <= kSubMaxSyms symbol codes on upload and packs the K x K int16 table densely
+// (row stride K), so the cell's gather is one add and one 16-bit LDS read.
+constexpr int kMatchSub = 3;
+constexpr int kSubMaxSyms = 64;
 
 // Internal per-pair flags (never returned: the int32 redo clears them).  kFlagRetry: a T16 SW
 // fill found a maximum above FillParams::retry_above, where a 16-bit candidate may have wrapped,
@@ -116,6 +122,10 @@ struct FillParams {
     // its f16 cells (SW; every value exact below 2048, pairs above kSo2F16RetryAbove re-run): 1 the
     // 5-op cell on f16 integers, 2 the 4-op cell on values scaled by 2^-11 with F kept per row
     uint32_t so2_f16;
+    // kMatchSub: the K x K int16 substitution table over symbol codes, row stride sub_k = K (the
+    // sequences hold codes); copied to LDS where kMatchLut keeps its bit table
+    const int16_t* submat;
+    uint32_t sub_k;
 };
 // the f16 cell's retry threshold on (sampled maximum - kSoSlack Gap): below it every value of the
 // pair stayed below 2048 (sa_fill_so2.hip)
@@ -218,6 +228,10 @@ struct TbParams {
     // fill stream, sa_api.hip tb_on_fill): keep_redo (the int32 walk) leaves kFlagRedo on the pairs
     // it walked, clear_redo (the T16 walk) skips those pairs and clears the bit (tb_release).
     int keep_redo, clear_redo;
+    // matrix calls (kMatchSub fills): the walk's diagonal term, submat[a * sub_k + b] over symbol
+    // codes; lutbits then only labels the op ('M' / 'S')
+    const int16_t* submat;
+    uint32_t sub_k;
 };
 // SA_FLAG_TIMEOUT: a SPLIT band's bounded wait for its producer expired (results invalid)
 
@@ -232,6 +246,7 @@ struct FillVariant {
     bool so = false;     // score-only T16 SW chunk-max fill (edge stream instead of records)
     bool so2 = false;    // score-only SW with two pairs per wave (sa_fill_so2.hip)
     bool norec = false;  // the score calls' int32 fill: no flags, no record stores (fill_body NOREC)
+    bool sub = false;    // kMatchSub (the matrix calls): int32 cell, allow-mismatch; lut / bits are ignored
 };
 hipError_t launch_fill(int algo, const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream);
 hipError_t launch_fill_sw(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
@@ -244,6 +259,17 @@ hipError_t launch_fill_nw_score(const FillVariant& v, const FillParams& p, uint3
 hipError_t launch_fill_lg_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
 hipError_t launch_fill_gg_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
 hipError_t launch_fill_score(int algo, const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream);
+// The kMatchSub fills (FillVariant::sub), recording and record-free, one translation unit each
+// (sa_fill_*_sub.hip, sa_fill_*_sub_score.hip); launch_fill_sub picks by algo and v.norec.
+hipError_t launch_fill_sw_sub(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_nw_sub(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_lg_sub(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_gg_sub(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_sw_sub_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_nw_sub_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_lg_sub_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_gg_sub_score(const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t s);
+hipError_t launch_fill_sub(int algo, const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream);
 // The last kernel of a score call (sa_score_batch*): no walk follows the fills, so this clears what
 // a walk would have -- the internal flags (kFlagRetry / kFlagRerun / kFlagRedo) and the end-cell
 // replay's `reserved` word -- and writes the score contract's start = (-1, -1), nops = 0.
@@ -335,6 +361,8 @@ __device__ __forceinline__ bool seg_take(const TbParams& P, const sa_result& res
 // inject (tests only): overwrite the exit records between the two kernels
 hipError_t launch_traceback_seg(int algo, int R, bool lut, const TbParams& p, hipStream_t stream, bool inject = false);
 hipError_t launch_traceback(int algo, int R, bool lut, const TbParams& p, hipStream_t stream);
+// The one-lane-per-pair walk of a matrix call (p.submat set; lutbits labels the ops).
+hipError_t launch_traceback_sub(int algo, int R, const TbParams& p, hipStream_t stream);
 // One wave per pair (sa_traceback_wave.hip): the few-pairs traceback.
 hipError_t launch_traceback_wave(int algo, int R, bool lut, const TbParams& p, hipStream_t stream);
 hipError_t launch_endcell(int algo, int R, const EndcellParams& p, hipStream_t stream);

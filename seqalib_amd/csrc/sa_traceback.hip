@@ -65,7 +65,9 @@ __device__ unsigned long long g_tb_stats[8];
 #endif
 
 // TAG: tagged affine records (T16 Gotoh fills, one byte per cell; sa_layout.h t16a_flags).
-template <int ALG, int R, bool LUT, bool TAG = false>
+// SUB: a matrix call's walk (SW / LocalGotoh, whose V steps back by the substitution term): the
+// sequences hold symbol codes, the term is P.submat[a * K + b] and lutbits only labels the op.
+template <int ALG, int R, bool LUT, bool TAG = false, bool SUB = false>
 __global__ __launch_bounds__(64) void traceback_kernel(TbParams P) {   // tb_mine: sa_internal.h
     constexpr int BPC = record_bpc(ALG, R, TAG), BPS = R * BPC / 8, SPP = 16 / BPS;
     static_assert(BPS >= 1 && BPS <= 16 && (SPP & (SPP - 1)) == 0, "one packet per step record");
@@ -93,6 +95,8 @@ __global__ __launch_bounds__(64) void traceback_kernel(TbParams P) {   // tb_min
     // Locals only below: lambdas capturing P or a Geom by reference keep them on the stack.
     const uint64_t band_stride = make_geom(ALG, R, P.max_m, P.max_n, tagged).band_stride;
     const uint32_t* const lutbits = P.lutbits;
+    const int16_t* const submat = P.submat;
+    const uint32_t sub_k = P.sub_k;
     const uint8_t* dir = P.dirs + (uint64_t)slot * P.dir_slot;
     tb_glb_u8* ops = (tb_glb_u8*)(P.ops + o1 + o2 + pidx);
     const bool allow = P.allow != 0;
@@ -193,6 +197,11 @@ __global__ __launch_bounds__(64) void traceback_kernel(TbParams P) {   // tb_min
     // match bit is the record's fX position under fD, see sa_fill_impl.h kMatchBits)
     const bool vrec = P.vrec != 0;
     auto diag = [&](int i, int j, uint32_t f) __attribute__((always_inline)) -> int {
+        if constexpr (SUB) {
+            const uint8_t ca = seqbyte(kTbSeqOff1, a1, s1, i - 1), cb2 = seqbyte(kTbSeqOff2, a2, s2, j - 1);
+            emit(tb_match<LUT>(lutbits, ca, cb2) ? 'M' : 'S');
+            return (int)submat[(uint32_t)ca * sub_k + cb2];
+        }
         const bool v = vrec ? ((f >> 2) & 1u) != 0
                             : tb_match<LUT>(lutbits, seqbyte(kTbSeqOff1, a1, s1, i - 1), seqbyte(kTbSeqOff2, a2, s2, j - 1));
         emit(v ? 'M' : (allow ? 'S' : 'X'));
@@ -246,16 +255,23 @@ __global__ __launch_bounds__(64) void traceback_kernel(TbParams P) {   // tb_min
                         if (ALG == SA_SW ? (!inner || V == 0) : !(i > 0 || j > 0)) { fin = true; break; }
                         uint32_t f = 1u;   // NW edges: j == 0 -> up (H[i][0] == H[i-1][0] + Gap), i == 0 -> left
                         bool v = false;
+                        int sub = 0;   // SUB: the substitution term of (i, j)
                         if (inner) {
                             f = lin();
-                            v = vrec ? (f & 1u) != 0
-                                     : tb_match<LUT>(lutbits, seqbyte(kTbSeqOff1, a1, s1, i - 1), seqbyte(kTbSeqOff2, a2, s2, j - 1));
+                            if constexpr (SUB) {
+                                const uint8_t ca = seqbyte(kTbSeqOff1, a1, s1, i - 1), cb2 = seqbyte(kTbSeqOff2, a2, s2, j - 1);
+                                v = tb_match<LUT>(lutbits, ca, cb2);
+                                sub = (int)submat[(uint32_t)ca * sub_k + cb2];
+                            } else {
+                                v = vrec ? (f & 1u) != 0
+                                         : tb_match<LUT>(lutbits, seqbyte(kTbSeqOff1, a1, s1, i - 1), seqbyte(kTbSeqOff2, a2, s2, j - 1));
+                            }
                         } else if (i == 0) {
                             f = 0u;
                         }
                         const bool dg = (f & 2u) != 0, up = !dg && (f & 1u);
                         emit(dg ? (v ? 'M' : (allow ? 'S' : 'X')) : (up ? 'U' : 'L'));
-                        if constexpr (ALG == SA_SW) V -= dg ? (v ? MA : MI) : G;
+                        if constexpr (ALG == SA_SW) V -= dg ? (SUB ? sub : (v ? MA : MI)) : G;
                         i -= (dg || up) ? 1 : 0;
                         j -= up ? 0 : 1;
                     } else if constexpr (ALG == SA_LOCAL_GOTOH) {
@@ -361,6 +377,26 @@ hipError_t launch_traceback(int algo, int R, bool lut, const TbParams& p, hipStr
     return hipErrorInvalidValue;
 }
 
+// Matrix calls: NW and GlobalGotoh walks read no substitution term, so the table-labelled (LUT)
+// kernels above serve them; SW and LocalGotoh take the SUB kernels.
+hipError_t launch_traceback_sub(int algo, int R, const TbParams& p, hipStream_t stream) {
+    if (!p.submat || !p.lutbits || p.tagged || p.vrec || !p.allow) return hipErrorInvalidValue;
+    if (algo == SA_NW || algo == SA_GLOBAL_GOTOH) return launch_traceback(algo, R, true, p, stream);
+    const dim3 block(64);
+    const dim3 grid((p.count + 63) / 64);
+#define SA_TBS(AA, RR)                                                                                  \
+    if (algo == AA && R == RR) {                                                                        \
+        hipLaunchKernelGGL((traceback_kernel<AA, RR, true, false, true>), grid, block, 0, stream, p);   \
+        return hipGetLastError();                                                                       \
+    }
+#define SA_TBS_A(AA) SA_TBS(AA, 1) SA_TBS(AA, 2) SA_TBS(AA, 4) SA_TBS(AA, 8) SA_TBS(AA, 16)
+    SA_TBS_A(SA_SW)
+    SA_TBS_A(SA_LOCAL_GOTOH)
+#undef SA_TBS_A
+#undef SA_TBS
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_fill(int algo, const FillVariant& v, const FillParams& p, uint32_t grid,
                        hipStream_t stream) {
     switch (algo) {
@@ -368,6 +404,16 @@ hipError_t launch_fill(int algo, const FillVariant& v, const FillParams& p, uint
         case SA_NW: return launch_fill_nw(v, p, grid, stream);
         case SA_LOCAL_GOTOH: return launch_fill_lg(v, p, grid, stream);
         case SA_GLOBAL_GOTOH: return launch_fill_gg(v, p, grid, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_fill_sub(int algo, const FillVariant& v, const FillParams& p, uint32_t grid, hipStream_t stream) {
+    switch (algo) {
+        case SA_SW: return v.norec ? launch_fill_sw_sub_score(v, p, grid, stream) : launch_fill_sw_sub(v, p, grid, stream);
+        case SA_NW: return v.norec ? launch_fill_nw_sub_score(v, p, grid, stream) : launch_fill_nw_sub(v, p, grid, stream);
+        case SA_LOCAL_GOTOH: return v.norec ? launch_fill_lg_sub_score(v, p, grid, stream) : launch_fill_lg_sub(v, p, grid, stream);
+        case SA_GLOBAL_GOTOH: return v.norec ? launch_fill_gg_sub_score(v, p, grid, stream) : launch_fill_gg_sub(v, p, grid, stream);
         default: return hipErrorInvalidValue;
     }
 }

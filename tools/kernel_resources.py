@@ -23,7 +23,7 @@ BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelIL
 SO2 = re.compile(r"Function Name: _ZN2sa15fill_so2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
 CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
-MM = ["eq", "lut", "bits"]
+MM = ["eq", "lut", "bits", "sub"]
 
 
 def remarks(unit):
