@@ -12,6 +12,8 @@
  *
  * Parity is PINNED: tests/test_oracle_golden.py checks this restatement against golden vectors
  * produced by the unmodified reference (oracle/_ref, tests/golden/make_golden.py).
+ * Pinned scoring regimes: gap < 0 < match, mismatch < 0 (kat / random / large / hirschberg /
+ * myersmiller.jsonl) and the scorings outside it of tests/util.py REGIME_* (regimes.jsonl).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library,
  * and only as the checker / baseline — never as the product path.

@@ -5,6 +5,7 @@ Runs ONLY in the build container, where /root/reference exists: `make ref` compi
 oracle/ref_harness.cpp against /root/reference/include into oracle/_ref/libsaref.so; this script
 drives it through ctypes and writes JSON-lines fixtures (inputs + expected outputs — data, no
 reference source).  Usage:  python tests/golden/make_golden.py
+(--only-mm, --only-hirschberg, --only-regimes rewrite one file each.)
 
 Corpus:
   * the README / test/Test.cpp known answer (NW, ScoringSystem(-1,2), AAAGAATGCAT / AAACTCAT);
@@ -122,6 +123,8 @@ def seq_of(spec) -> bytes:
         return ref_dna(spec["seed"], spec["len"])
     if spec["kind"] == "mut":
         return py_mutate(seq_of(spec["src"]), spec["seed"])
+    if spec["kind"] == "rep":
+        return spec["unit"].encode() * spec["count"]
     if spec["kind"] == "withN":
         b = bytearray(seq_of(spec["src"]))
         for p in range(spec["phase"], len(b), spec["every"]):
@@ -214,11 +217,105 @@ def mm_vectors():
     return mm
 
 
+# ------------------------------------------------------------------------- scoring regimes
+# regimes.jsonl: every scoring of util.REGIME_LINEAR under SW, NW and Hirschberg and every one of
+# util.REGIME_AFFINE under LocalGotoh, GlobalGotoh and Myers-Miller, equal<char>, on REGIME_PAIRS.
+# These scorings are outside gap < 0 < match, mismatch < 0, where the reference is still defined
+# but where its LocalGotoh walk may never end (gap_extend > 0).  So each (algorithm, scoring) group
+# runs in a child process with a time limit, and a pair on which the oracle's walk finds no move
+# (rc == -3: the reference would loop there) is never given to the reference; it is written as a
+# diverged record (null) with no expected output.  The alignment strings are stored as digests.
+REGIME_GROUP_TIMEOUT = 120
+
+
+def rep(unit, count):
+    return {"kind": "rep", "unit": unit, "count": count}
+
+
+_R70 = {"kind": "dna", "seed": 8_000_000_001, "len": 70}
+_R55 = {"kind": "dna", "seed": 8_000_000_003, "len": 55}
+_R62 = {"kind": "dna", "seed": 8_000_000_004, "len": 62}
+REGIME_PAIRS = [
+    # known-answer pairs (a subset of TEST_CPP_PAIRS)
+    ("AATCG", "AACG"), ("CTGAAGCGG", "CTCAAGCGTAGTCC"), ("AGTAC", "AAG"), ("ACGGTTGC", "AGCGTC"), ("AGTC", "GACT"),
+    ("AAAGAATGCAT", "AAACTCAT"), ("A", "C"),
+    # empty sides, homopolymers, periodic sequences
+    ("", "ACGT"), ("ACGT", ""), ("", ""), (rep("A", 40), rep("A", 37)), (rep("A", 33), rep("C", 35)),
+    (rep("AC", 20), rep("CA", 17)), (rep("ACGT", 16), rep("ACGT", 15)),
+    # random and mutated DNA
+    (_R70, {"kind": "dna", "seed": 8_000_000_002, "len": 64}),
+    (_R55, {"kind": "mut", "src": _R55, "seed": 31}),
+    ({"kind": "mut", "src": _R62, "seed": 32}, _R62),
+]
+
+
+def regime_groups():
+    from util import REGIME_AFFINE, REGIME_LINEAR
+    return [(algo, sc) for algo in ("sw", "nw", "hb") for sc in REGIME_LINEAR] + \
+           [(algo, sc) for algo in ("lg", "gg", "mm") for sc in REGIME_AFFINE]
+
+
+def regime_group(k):
+    """Child process: the record of group k, one JSON line on stdout: per pair of REGIME_PAIRS
+    [score, max_row, max_col, len, digest of the three alignment strings], or null where diverged."""
+    from util import oracle_align
+    algo, sc = regime_groups()[k]
+    assert all(x in TEST_CPP_PAIRS for x in REGIME_PAIRS[:7])
+    out = []
+    for s1spec, s2spec in REGIME_PAIRS:
+        s1, s2 = seq_of(s1spec), seq_of(s2spec)
+        assert len(s1) <= 70 and len(s2) <= 70 and not lg_hack(len(s1), len(s2))
+        if oracle_align(ALGO[algo], sc, s1, s2)["rc"] == -3:
+            out.append(None)
+            continue
+        score, mr, mc, rows = ref_align(ALGO[algo], sc, "equal", s1, s2)
+        # MyersMillerSA exposes no score (SAMyersMiller.h:412-420)
+        out.append([None if algo == "mm" else score, mr, mc, len(rows[0]), rows_digest(*rows)])
+    print(json.dumps({"algo": algo, "scoring": list(sc), "out": out}, separators=(",", ":")), flush=True)
+
+
+def regime_vectors():
+    """The lines of regimes.jsonl: the pair table, then one record per (algorithm, scoring) group
+    (util.load_regimes expands them into entries of the other fixtures' form)."""
+    import subprocess
+    from util import REGIME_DIVERGING
+    rows, failed = [{"pairs": [list(p) for p in REGIME_PAIRS]}], []
+    for k, (algo, sc) in enumerate(regime_groups()):
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--regime-group", str(k)],
+                               stdout=subprocess.PIPE, timeout=REGIME_GROUP_TIMEOUT)
+        except subprocess.TimeoutExpired:
+            failed.append((algo, sc, "time limit"))
+            continue
+        if p.returncode != 0:
+            failed.append((algo, sc, f"exit {p.returncode}"))
+            continue
+        e = json.loads(p.stdout.decode())
+        assert len(e["out"]) == len(REGIME_PAIRS), (algo, sc)
+        if None in e["out"]:
+            assert (ALGO[algo], tuple(sc)) == REGIME_DIVERGING, ("unexpected diverged record", algo, sc)
+        rows.append(e)
+    if failed:
+        sys.exit(f"regime groups that did not finish: {failed}")
+    return rows
+
+
 def main():
     global L
     if not os.path.exists(REF_SO):
         sys.exit("oracle/_ref/libsaref.so missing: run `make ref` (needs /root/reference)")
     L = ref_lib()
+    if "--regime-group" in sys.argv:
+        regime_group(int(sys.argv[sys.argv.index("--regime-group") + 1]))
+        return
+    if "--only-regimes" in sys.argv:
+        rows = regime_vectors()
+        with open(os.path.join(HERE, "regimes.jsonl"), "w") as f:
+            for e in rows:
+                f.write(json.dumps(e, separators=(",", ":")) + "\n")
+        outs = [o for e in rows[1:] for o in e["out"]]
+        print(f"regimes.jsonl: {len(outs)} vectors, {outs.count(None)} diverged")
+        return
     if "--only-mm" in sys.argv:
         rows = mm_vectors()
         with open(os.path.join(HERE, "myersmiller.jsonl"), "w") as f:

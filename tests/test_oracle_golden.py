@@ -59,6 +59,30 @@ def test_oracle_myers_miller():
         check(e)
 
 
+def test_oracle_regimes():
+    """Scorings outside gap < 0 < match, mismatch < 0 (util.REGIME_LINEAR / REGIME_AFFINE, under
+    SW / NW / Hirschberg and LocalGotoh / GlobalGotoh / Myers-Miller): the oracle equals every vector
+    of the unmodified reference, and its walk finds no move (rc == -3, where the reference's loops
+    forever and was therefore not run) on exactly the records marked diverged -- all of them
+    LocalGotoh under the one scoring with gap_extend > 0."""
+    from util import REGIME_AFFINE, REGIME_DIVERGING, REGIME_LINEAR, load_regimes
+    reg = load_regimes()
+    groups = {(e["algo"], tuple(e["scoring"])) for e in reg}
+    want = {(a, sc) for a in ("sw", "nw", "hb") for sc in REGIME_LINEAR}
+    want |= {(a, sc) for a in ("lg", "gg", "mm") for sc in REGIME_AFFINE}
+    assert groups == want
+    diverged = 0
+    for e in reg:
+        if e.get("diverged"):
+            assert (ALGOS[e["algo"]], tuple(e["scoring"])) == REGIME_DIVERGING
+            s1, s2 = golden_sequences(e)
+            assert oracle_align(ALGOS[e["algo"]], e["scoring"], s1, s2)["rc"] == -3, e["id"]
+            diverged += 1
+        else:
+            check(e)
+    assert diverged > 0 and len(reg) - diverged > 2500
+
+
 def test_oracle_random():
     for e in RND:
         check(e)

@@ -20,6 +20,39 @@ REF_SO = os.path.join(ROOT, "oracle", "_ref", "libsaref.so")
 
 ALGOS = {"sw": 0, "nw": 1, "lg": 2, "gg": 3, "hb": 4, "mm": 5}
 
+# ---------------------------------------------------------------- scoring regimes
+# Scorings outside gap < 0 < match, mismatch < 0: what the kernel-selection rules of sa_api.hip
+# (t16_mode, t16_mode_affine, keyed_ok) and sa_dc.h (dc16_plan) admit, and the values just past
+# each rule.  tests/golden/regimes.jsonl pins the oracle to the reference on every one of them;
+# tests/test_gpu_regimes.py runs the kernels on them.
+REGIME_LINEAR = [   # SW, NW, Hirschberg
+    # inside the 16-bit rules: match 0 / < 0, mismatch = match, 0 <= mismatch < match, the corners
+    (-1, 0, -1), (-1, -1, -2), (-1, 1, 0), (-1, 1, 1), (-1, 2, 1), (-2, 2, 2), (-3, 31, -32), (-4096, 31, -32),
+    (-1, 0, -1, False), (-1, -1, -2, False),
+    # gap = 0 (16-bit for NW, int32 for SW)
+    (0, 1, -1), (0, 1, 0), (0, 0, 0), (0, 3, 3), (0, 1), (0, 1, -1, False),
+    # mismatch > match, gap > 0
+    (-1, 1, 2), (-1, -2, -1), (1, 1, -1), (1, -1, -1), (2, 1, -3), (1, 2), (1, 2, -1, False),
+    # just past the 16-bit rules
+    (-700, 1000, -900), (-4097, 31, -32), (-1, 32, -1), (-1, 31, -33),
+    # the edges of the linear-space 16-bit sweeps
+    (-1, 127, -128), (-1, 128, -1), (-1, 1, -129),
+]
+REGIME_AFFINE = [   # LocalGotoh, GlobalGotoh, Myers-Miller
+    (-3, -1, 0, -1, True), (-3, -1, 1, 0, True), (-3, -1, 1, 1, True), (-3, -1, -1, -2, True), (-3, -1, 15, -16, True),
+    (-2048, -512, 15, -16, True),
+    (-3, -1, 0, -1, False), (0, -1, 1, -1, False),
+    (-3, 0, 1, -1, True), (0, 0, 1, -1, True), (-3, 0, 1, -1, False),
+    (1, -1, 1, -1, True), (2, -1, 1, -1, True), (-3, 1, 1, -1, True),
+    (-3, -1, 1, 2, True), (-3, -1, 2, 2, True), (0, -2, 3, 1, True), (-3, -1, 16, -17, True), (-2049, -513, 15, -16, True),
+    (-6000, -5000, 1, -1, True), (-6000, -5000, 1, -1, False), (-3, -5, 1, -1, True),
+    (-3, -1, 127, -128, True), (-3, -1, 128, -1, True),
+]
+# the one regime scoring under which the reference's LocalGotoh walk may not terminate (the oracle
+# returns rc == -3, the engine sets SA_FLAG_DIVERGED)
+REGIME_DIVERGING = (2, (-3, 1, 1, -1, True))
+LG_HACK_SIZES = ((314, 288), (60, 57), (61, 58))   # SALocalGotoh.h:484-488
+
 
 # ------------------------------------------------------------------ std::mt19937_64 (pure Python)
 class MT64:
@@ -282,6 +315,23 @@ def load_golden(name: str):
         return [json.loads(line) for line in f if line.strip()]
 
 
+def load_regimes():
+    """regimes.jsonl (a pair table, then per (algorithm, scoring) group one output per pair) as entries
+    of the other fixtures' form; a pair the reference was not run on is {"diverged": True}."""
+    head, *groups = load_golden("regimes.jsonl")
+    out = []
+    for g in groups:
+        for pi, ((s1, s2), o) in enumerate(zip(head["pairs"], g["out"])):
+            e = {"id": f"r{pi}/{g['algo']}/{'_'.join(str(int(x)) for x in g['scoring'])}/equal", "algo": g["algo"],
+                 "scoring": g["scoring"], "match": "equal", "s1": s1, "s2": s2}
+            if o is None:
+                e["diverged"] = True
+            else:
+                e["score"], e["max_row"], e["max_col"], e["len"], e["rows_sha"] = o
+            out.append(e)
+    return out
+
+
 def golden_sequences(entry) -> Tuple[bytes, bytes]:
     """Materialise an entry's sequences (literal, or regenerated from its generator spec)."""
     def one(spec):
@@ -294,6 +344,8 @@ def golden_sequences(entry) -> Tuple[bytes, bytes]:
         if kind == "mut":
             from seqalib_amd import synth_mutate
             return synth_mutate(one(spec["src"]), spec["seed"])
+        if kind == "rep":     # a unit repeated
+            return spec["unit"].encode("latin-1") * spec["count"]
         if kind == "withN":   # every k-th symbol replaced by N
             b = bytearray(one(spec["src"]))
             for p in range(spec["phase"], len(b), spec["every"]):
