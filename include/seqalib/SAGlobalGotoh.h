@@ -45,6 +45,30 @@ public:
         return out;
     }
 
+    // Extension: banded GlobalGotoh (sa_align_batch_banded_affine / sa_score_batch_banded_affine): only
+    // the cells within `band` diagonals of each pair's corner-to-corner corridor, O((m + n) * band) work
+    // and memory per pair.  With band >= max(m, n) the result is getAlignments(pairs).  Needs
+    // gap_extend <= 0 and at most 2048 band diagonals inside a pair's matrix.  Byte-sized symbols, or
+    // batches of at most 256 distinct symbols; a band that does not fit 32 bits throws
+    // std::runtime_error, as does setSubstitution() with a band.
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band) {
+        std::vector<sa_result> res;
+        auto out = seqalib::detail::run<SA_GLOBAL_GOTOH, GlobalGotohSA, ContainerType, Ty, Blank>(*this, pairs, res,
+                                                                                                 seqalib::detail::band_of(band));
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band) {
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_GLOBAL_GOTOH, GlobalGotohSA, ContainerType, Ty>(*this, pairs, res,
+                                                                                      seqalib::detail::band_of(band));
+        std::vector<ScoreSystemType> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.push_back(r.score);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
 
     ScoreSystemType getScore() const { return LastScore; }
 };

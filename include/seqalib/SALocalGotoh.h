@@ -63,12 +63,50 @@ public:
         return out;
     }
 
+    // Extension: banded LocalGotoh (sa_align_batch_banded_affine / sa_score_batch_banded_affine): only
+    // the cells within `band` diagonals of each pair's corner-to-corner corridor, O((m + n) * band) work
+    // and memory per pair; the end cell is the last in-band maximum.  This is the raw path: the size-hack
+    // shapes are aligned as LocalGotoh like every other shape, so with band >= max(m, n) the result is
+    // getAlignments(pairs) for every other shape.  Needs gap_extend <= 0 and at most 2048 band diagonals
+    // inside a pair's matrix.  Byte-sized symbols, or batches of at most 256 distinct symbols; a band
+    // that does not fit 32 bits throws std::runtime_error, as does setSubstitution() with a band.
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band) {
+        std::vector<sa_result> res;
+        auto out = seqalib::detail::run<SA_LOCAL_GOTOH, LocalGotohSA, ContainerType, Ty, Blank>(*this, pairs, res,
+                                                                                               seqalib::detail::band_of(band));
+        if (!res.empty()) {
+            MaxRow = res.back().end_i;
+            MaxCol = res.back().end_j;
+            MaxScore = res.back().score;
+        }
+        return out;
+    }
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band) {
+        std::vector<sa_result> res;
+        scoreBatch(pairs, res, seqalib::detail::band_of(band));
+        std::vector<ScoreSystemType> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.push_back(r.score);
+        return out;
+    }
+    std::vector<std::pair<size_t, size_t>> getEndCells(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                       size_t band) {
+        std::vector<sa_result> res;
+        scoreBatch(pairs, res, seqalib::detail::band_of(band));
+        std::vector<std::pair<size_t, size_t>> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.emplace_back((size_t)r.end_i, (size_t)r.end_j);
+        return out;
+    }
+
     ScoreSystemType getScore() const { return MaxScore; }
     std::pair<size_t, size_t> getEndCell() const { return {MaxRow, MaxCol}; }
 
 private:
-    void scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res) {
-        seqalib::detail::run_scores<SA_LOCAL_GOTOH, LocalGotohSA, ContainerType, Ty>(*this, pairs, res);
+    void scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
+                    long long band = seqalib::detail::kNoBand) {
+        seqalib::detail::run_scores<SA_LOCAL_GOTOH, LocalGotohSA, ContainerType, Ty>(*this, pairs, res, band);
         if (!res.empty()) {
             MaxRow = res.back().end_i;
             MaxCol = res.back().end_j;

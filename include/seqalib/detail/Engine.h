@@ -383,8 +383,10 @@ void pack_batch(PackedBatch<Ty>& pk, const std::vector<std::pair<ContainerType*,
 // is called, on this thread, as soon as a range's results and op streams are in res / ops (the
 // other paths report the whole batch once at the end).
 // band >= 0: the banded call of that half-width (sa_align_batch_banded / sa_score_batch_banded), on
-// this thread's context; it takes byte symbols or a symbol table, not per-pair bitmaps.
+// this thread's context; it takes byte symbols or a symbol table, not per-pair bitmaps.  LocalGotoh
+// and GlobalGotoh take the affine forms (sa_align_batch_banded_affine / sa_score_batch_banded_affine).
 constexpr long long kNoBand = -1;
+inline bool banded_is_affine(int algo) { return algo == SA_LOCAL_GOTOH || algo == SA_GLOBAL_GOTOH; }
 constexpr size_t kBandedMaxSymbols = 256;
 inline uint32_t band_arg(long long band) {
     if (band > 0xffffffffLL) throw std::runtime_error("seqalib: band does not fit 32 bits");
@@ -479,9 +481,11 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
     tm.lap("match table + buffers");
     if (band != kNoBand) {
-        check(sa_align_batch_banded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
-                                    has_fn ? lut.data() : nullptr, band_arg(band), res.data(), ops.data(), cap),
-              "sa_align_batch_banded");
+        const bool aff = banded_is_affine(algo);
+        check((aff ? sa_align_batch_banded_affine : sa_align_batch_banded)(
+                  context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, has_fn ? lut.data() : nullptr,
+                  band_arg(band), res.data(), ops.data(), cap),
+              aff ? "sa_align_batch_banded_affine" : "sa_align_batch_banded");
         if (on_chunk && n) on_chunk(0, n);
     } else if (sa_multi* mg = multi_context()) {
         const int rc = sa_multi_align_batch(mg, algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
@@ -535,9 +539,11 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
         banded_needs_table(coder.overflow);
         std::vector<uint8_t> lut;
         if (has_fn) lut = build_lut(coder, fn);
-        check(sa_score_batch_banded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
-                                    has_fn ? lut.data() : nullptr, band_arg(band), res.data()),
-              "sa_score_batch_banded");
+        const bool aff = banded_is_affine(algo);
+        check((aff ? sa_score_batch_banded_affine : sa_score_batch_banded)(
+                  context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, has_fn ? lut.data() : nullptr,
+                  band_arg(band), res.data()),
+              aff ? "sa_score_batch_banded_affine" : "sa_score_batch_banded");
         tm.lap("sa_score_batch_banded (GPU)");
     } else if (coder.overflow) {   // more than 256 distinct symbols: the generic-Ty (bitmap) path
         std::vector<uint64_t> bo;

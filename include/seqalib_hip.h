@@ -280,6 +280,63 @@ int sa_score_batch_banded(sa_ctx* ctx, int algo, const sa_scoring* scoring,
 int sa_banded_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs,
                          int* cells_per_lane, int* pairs_per_wave, uint64_t* workspace_bytes_per_pair);
 
+/* Banded LocalGotoh / GlobalGotoh (affine gaps): the band, the cost and the calling contract of
+ * sa_align_batch_banded / sa_score_batch_banded, for SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH.
+ * Band.  As above: lo = min(0, n - m) - w, hi = max(0, n - m) + w, clipped to the matrix; cell (i, j)
+ *   exists iff lo <= j - i <= hi.
+ * Recurrence.  That of the raw (unhacked) Gotoh path of sa_align_batch, three values per cell:
+ *     X(i, j) = max(M(i-1, j) + gap_open + gap_extend, X(i-1, j) + gap_extend)      (vertical gap)
+ *     Y(i, j) = max(M(i, j-1) + gap_open + gap_extend, Y(i, j-1) + gap_extend)      (horizontal gap)
+ *     M(i, j) = max(M(i-1, j-1) + match / mismatch, X(i, j), Y(i, j) [, 0 for LocalGotoh])
+ *   Borders: M(i, 0) = M(0, j) = 0 for LocalGotoh; gap_open + k * gap_extend for GlobalGotoh with
+ *   M(0, 0) = 0; X = Y = -10000 on every border cell (the reference's constant).
+ *   A term that would read a cell outside the band is no candidate: X(i, j) does not exist when
+ *   (i-1, j) is outside the band, Y(i, j) does not exist when (i, j-1) is; a non-existent X or Y takes
+ *   no part in M's maximum and never compares equal in the walk; if (i-1, j) exists but its X does
+ *   not, X(i, j) is the open term alone (Y likewise).
+ * Walk.  The reference's state machine (type 0 in M, 1 in a vertical gap, 2 in a horizontal one):
+ *   in type 0 the diagonal is tried first, then M == X (to type 1), then M == Y (to type 2); in type
+ *   1 / 2 the extend term is tried before the open term (which returns to type 0); a comparison
+ *   against a non-existent value is false.  GlobalGotoh borders: j == 0 gives 'U', i == 0 gives 'L'.
+ *   Op codes and traceback order as in sa_align_batch.  With gap_extend <= 0 the walk always finds an
+ *   equal candidate and, for LocalGotoh, never emits 'u' / 'l'.
+ * LocalGotoh end cell: the last in-band cell in row-major order holding the maximum; score = M
+ *   there.  An empty input gives what the raw unbanded path gives: score 0, end (0, 0), no ops.
+ * The LocalGotoh size hack is never applied (as in the matrix and device calls): SA_FLAG_SIZE_HACK
+ *   never appears, flags = 0.
+ * Score call: start = (-1, -1), nops = 0, reserved = 0, flags = 0; no records, no walk.
+ * With band >= max(m, n) every result field and op equals the unbanded raw Gotoh result; for any
+ *   band the score is <= the unbanded score.
+ * Status codes (these checks are made before the context is looked at, so they give the same status
+ * with a NULL context; a NULL context with valid arguments: SA_ERR_ARG):
+ *   algo: SA_ERR_UNSUPPORTED for the four other algorithms, SA_ERR_ARG for an invalid value.
+ *   gap_extend > 0: SA_ERR_UNSUPPORTED (gap_open may have any sign).
+ *   allow_mismatch == 0 with band == 0: SA_ERR_UNSUPPORTED.     band >= 2^31: SA_ERR_ARG.
+ *   SA_ERR_UNSUPPORTED also for a pair with
+ *     (m + n + 1) * max(|gap_open| + |gap_extend|, |match|, |mismatch|) + 10000 >= 2^29 (mismatch
+ *       counted only when allowed),
+ *     a sequence of >= 2^24 symbols,
+ *     more than 2048 band diagonals inside its matrix (min(hi, n) - max(lo, -m) + 1: three values per
+ *       cell fit the registers of one wave up to 16 cells per lane and step),
+ *     LocalGotoh: (m + 1) * that number of diagonals >= 2^31.
+ * sa_last_timings works after either call; sa_last_plan_ex reports SA_KERNEL_BANDED, the cells per
+ * lane and step of the widest variant the call used, 1 wave, and SA_RECORDS_BAND4 / SA_RECORDS_NONE. */
+int sa_align_batch_banded_affine(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const uint8_t* match_lut, uint32_t band,
+                                 sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_banded_affine(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const uint8_t* match_lut, uint32_t band, sa_result* results);
+/* sa_banded_plan_query for the affine calls: cells per lane and step R (1 .. 16), pairs per wave, and
+ * the pair's 4-bit records in an align call's launch, (m + n + 2 - max(lo, -m)) * 2 R L / 4 bytes
+ * rounded up to L words -- twice the linear call's for the same shape.  SA_ERR_UNSUPPORTED beyond
+ * 2048 diagonals inside the matrix and outside the other limits above. */
+int sa_banded_affine_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs,
+                                int* cells_per_lane, int* pairs_per_wave, uint64_t* workspace_bytes_per_pair);
+
 /* Substitution-matrix scoring: the diagonal move of cell (i, j) scores submat[a * 256 + b], a = Seq1
  * symbol i-1, b = Seq2 symbol j-1, instead of one of the two numbers match / mismatch.
  *   submat: a dense 256 x 256 int16 table on the host; it need not be symmetric, and only the entries
@@ -349,7 +406,7 @@ int sa_last_kernel_timings(sa_ctx* ctx, float* fill_kernel_ms, float* fill_strea
  * in LDS), reading and writing pinned host memory.  Such a call reports 0 fill launches to
  * sa_last_timings.  Environment: SEQALIB_TINY=0 sends them through the batch kernels. */
 #define SA_KERNEL_TINY 3
-#define SA_KERNEL_BANDED 4   /* sa_align_batch_banded / sa_score_batch_banded */
+#define SA_KERNEL_BANDED 4   /* sa_align_batch_banded / sa_score_batch_banded and their _affine forms */
 int sa_last_plan(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves);
 /* sa_last_plan plus what the fill stored for the traceback: SA_RECORDS_FLAGS (int32 equality
  * flags), SA_RECORDS_TAGS (T16 move tags per cell) or SA_RECORDS_SCORE_ONLY (score-only T16 SW fill:
@@ -360,6 +417,7 @@ int sa_last_plan(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves);
 #define SA_RECORDS_SCORE_ONLY 2
 #define SA_RECORDS_NONE 3   /* score calls on the int32 / small-call kernels: the fill stored nothing for a traceback */
 #define SA_RECORDS_BAND2 4  /* banded align calls: 2 bits per in-band cell, laid out by anti-diagonal */
+#define SA_RECORDS_BAND4 5  /* banded affine align calls: 4 bits per in-band cell */
 int sa_last_plan_ex(sa_ctx* ctx, int* kernel, int* rows_per_lane, int* waves, int* records);
 
 /* Plan of the int32 kernel for a batch (host-only query, no device needed): rows per lane R,

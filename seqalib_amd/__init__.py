@@ -46,6 +46,7 @@ SA_PIPELINE_DEPTH = 2   # pipelined device calls that may run at once (distinct 
 SA_RECORDS_FLAGS, SA_RECORDS_TAGS, SA_RECORDS_SCORE_ONLY = 0, 1, 2
 SA_RECORDS_NONE = 3   # score calls on the int32 / small-call kernels: nothing stored for a traceback
 SA_RECORDS_BAND2 = 4  # banded align calls: 2 bits per in-band cell, laid out by anti-diagonal
+SA_RECORDS_BAND4 = 5  # banded affine align calls: 4 bits per in-band cell
 SA_HOOK_HAND_TAG, SA_HOOK_POISON_WS, SA_HOOK_F16 = 1, 2, 3   # sa_test_hook (tests only)
 INT32_MIN = -(2 ** 31)
 
@@ -142,6 +143,9 @@ def load_library():
     L.sa_score_batch_banded.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32,
                                         vp]
     L.sa_banded_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p]
+    L.sa_align_batch_banded_affine.argtypes = L.sa_align_batch_banded.argtypes
+    L.sa_score_batch_banded_affine.argtypes = L.sa_score_batch_banded.argtypes
+    L.sa_banded_affine_plan_query.argtypes = L.sa_banded_plan_query.argtypes
     L.sa_score_plan_query.argtypes = [C.c_int, C.POINTER(_Scoring), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                       i32p, i32p, i32p, u64p]
     L.sa_align_batch_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
@@ -167,6 +171,7 @@ def load_library():
                "sa_score_batch_device", "sa_multi_score_batch", "sa_score_plan_query",
                "sa_last_timings", "sa_last_kernel_timings", "sa_last_plan", "sa_last_plan_ex", "sa_plan_query", "sa_plan_query_ex", "sa_synth_dna", "sa_synth_mutate", "sa_synth_dna_batch",
                "sa_align_batch_banded", "sa_score_batch_banded", "sa_banded_plan_query",
+               "sa_align_batch_banded_affine", "sa_score_batch_banded_affine", "sa_banded_affine_plan_query",
                "sa_align_batch_matrix", "sa_score_batch_matrix", "sa_matrix_plan_query",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
@@ -514,6 +519,16 @@ class Engine:
                             s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None):
         """Banded host-buffer batch (sa_align_batch_banded): NW / SW over the cells within `band`
         diagonals of each pair's corner-to-corner corridor.  Returns (results, ops) as align_packed."""
+        return self._align_banded_call("sa_align_batch_banded", algo, scoring, s1, off1, s2, off2, band, lut)
+
+    def align_banded_affine_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None):
+        """Banded affine host-buffer batch (sa_align_batch_banded_affine): LocalGotoh / GlobalGotoh over
+        the cells within `band` diagonals of each pair's corridor, raw path (no LocalGotoh size hack).
+        Returns (results, ops) as align_packed."""
+        return self._align_banded_call("sa_align_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
+
+    def _align_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut):
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
@@ -527,14 +542,22 @@ class Engine:
             lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
             lut_p = _ptr(lut)
         sc = scoring._c()
-        rc = self.L.sa_align_batch_banded(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                          npairs, lut_p, _band_arg(band), _ptr(res), _ptr(ops), ops_cap)
-        self._check(rc, "sa_align_batch_banded")
+        rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                 npairs, lut_p, _band_arg(band), _ptr(res), _ptr(ops), ops_cap)
+        self._check(rc, fn)
         return res[:npairs], ops
 
     def score_banded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                             s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Banded score batch (sa_score_batch_banded): the results array (start = -1, nops = 0)."""
+        return self._score_banded_call("sa_score_batch_banded", algo, scoring, s1, off1, s2, off2, band, lut)
+
+    def score_banded_affine_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Banded affine score batch (sa_score_batch_banded_affine): the results array (start = -1, nops = 0)."""
+        return self._score_banded_call("sa_score_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
+
+    def _score_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut):
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
@@ -546,16 +569,24 @@ class Engine:
             lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
             lut_p = _ptr(lut)
         sc = scoring._c()
-        rc = self.L.sa_score_batch_banded(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                          npairs, lut_p, _band_arg(band), _ptr(res))
-        self._check(rc, "sa_score_batch_banded")
+        rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                 npairs, lut_p, _band_arg(band), _ptr(res))
+        self._check(rc, fn)
         return res[:npairs]
 
     def align_banded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
                      lut: Optional[np.ndarray] = None) -> List[PairResult]:
         """align() through the banded call."""
+        return self._align_banded_pairs(self.align_banded_packed, algo, scoring, pairs, band, lut)
+
+    def align_banded_affine(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                            lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the banded affine call."""
+        return self._align_banded_pairs(self.align_banded_affine_packed, algo, scoring, pairs, band, lut)
+
+    def _align_banded_pairs(self, call, algo, scoring, pairs, band, lut):
         s1, off1, s2, off2 = pack_pairs(pairs)
-        res, ops = self.align_banded_packed(algo, scoring, s1, off1, s2, off2, band, lut)
+        res, ops = call(algo, scoring, s1, off1, s2, off2, band, lut)
         out = []
         for p in range(len(pairs)):
             o = int(off1[p] + off2[p]) + p
@@ -569,6 +600,12 @@ class Engine:
         """score() through the banded call."""
         s1, off1, s2, off2 = pack_pairs(pairs)
         return self._score_results(self.score_banded_packed(algo, scoring, s1, off1, s2, off2, band, lut))
+
+    def score_banded_affine(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                            lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the banded affine call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_banded_affine_packed(algo, scoring, s1, off1, s2, off2, band, lut))
 
     def align_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                             s2: np.ndarray, off2: np.ndarray, matrix, lut: Optional[np.ndarray] = None):
@@ -827,6 +864,17 @@ def banded_plan_query(algo: int, max_m: int, max_n: int, band: int, npairs: int 
     return R.value, ppw.value, ws.value
 
 
+def banded_affine_plan_query(algo: int, max_m: int, max_n: int, band: int, npairs: int = 1):
+    """banded_plan_query for the banded affine calls (sa_banded_affine_plan_query): cells per lane and
+    step (at most 16: up to 2048 diagonals inside the matrix), pairs per wave, bytes of 4-bit records."""
+    L = load_library()
+    R, ppw, ws = C.c_int(), C.c_int(), C.c_uint64()
+    rc = L.sa_banded_affine_plan_query(algo, max_m, max_n, _band_arg(band), npairs, C.byref(R), C.byref(ppw), C.byref(ws))
+    if rc:
+        raise SeqalibError(f"sa_banded_affine_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
+    return R.value, ppw.value, ws.value
+
+
 def matrix_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 20):
     """(kernel, R, W, workspace bytes per pair) of sa_align_batch_matrix for a batch of this shape with
     nsym distinct symbols (sa_matrix_plan_query; no GPU needed)."""
@@ -930,7 +978,8 @@ class _Aligner:
 
     def getAlignments(self, pairs: Sequence[Tuple[object, object]], band: Optional[int] = None) -> List[AlignedSequence]:
         """band: half-width of the banded call (NeedlemanWunschSA, HirschbergSA = NW, SmithWatermanSA;
-        the other aligners raise SeqalibError); None: the unbanded path."""
+        the other aligners raise SeqalibError -- LocalGotohSA and GlobalGotohSA band through
+        getBandedAlignments / getBandedScores instead); None: the unbanded path."""
         eng = _engine(self.device)
         if self.matrix is not None:
             if band is not None:
@@ -974,15 +1023,43 @@ class _Aligner:
 
     def getScores(self, pairs: Sequence[Tuple[object, object]], band: Optional[int] = None) -> List[int]:
         """The getScore() of every pair in one GPU pass with no traceback; getScore() afterwards is
-        the last pair's.  band: as getAlignments."""
+        the last pair's.  band: as getAlignments (it raises on the Gotoh classes: getBandedScores)."""
         return [r.score for r in self._score_results(pairs, band)]
 
 
 class _LocalAligner(_Aligner):
     def getEndCells(self, pairs: Sequence[Tuple[object, object]], band: Optional[int] = None) -> List[Tuple[int, int]]:
         """(MaxRow, MaxCol) of every pair -- the last row-major cell holding the maximum (band: the
-        last in-band one)."""
+        last in-band one; it raises on LocalGotohSA, whose banded form is getBandedEndCells)."""
         return [(r.end_i, r.end_j) for r in self._score_results(pairs, band)]
+
+
+class _BandedAffine:
+    """The banded affine calls on LocalGotohSA / GlobalGotohSA.  They are separate methods because
+    band= on getAlignments / getScores keeps raising for these classes.  Results are the raw path's
+    (no LocalGotoh size hack); a substitution matrix cannot be combined with a band."""
+
+    def _banded_affine_check(self):
+        if self.matrix is not None:
+            raise SeqalibError("a substitution matrix and a band cannot be combined")
+
+    def getBandedAlignments(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[AlignedSequence]:
+        self._banded_affine_check()
+        res = _engine(self.device).align_banded_affine(self.ALGO, self.scoring, pairs, band, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return [expand_ops(self.ALGO, a, b, r, self.blank) for (a, b), r in zip(pairs, res)]
+
+    def getBandedAlignment(self, seq1, seq2, band: int) -> AlignedSequence:
+        return self.getBandedAlignments([(seq1, seq2)], band)[0]
+
+    def _banded_score_results(self, pairs, band: int) -> List[PairResult]:
+        self._banded_affine_check()
+        res = _engine(self.device).score_banded_affine(self.ALGO, self.scoring, pairs, band, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return res
+
+    def getBandedScores(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[int]:
+        return [r.score for r in self._banded_score_results(pairs, band)]
 
 
 class SmithWatermanSA(_LocalAligner):
@@ -997,8 +1074,12 @@ class NeedlemanWunschSA(_Aligner):
     ALGO = SA_NW
 
 
-class LocalGotohSA(_LocalAligner):
+class LocalGotohSA(_LocalAligner, _BandedAffine):
     ALGO = SA_LOCAL_GOTOH
+
+    def getBandedEndCells(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[Tuple[int, int]]:
+        """(MaxRow, MaxCol) of every pair: the last in-band row-major cell holding the maximum."""
+        return [(r.end_i, r.end_j) for r in self._banded_score_results(pairs, band)]
 
 
 class HirschbergSA(_Aligner):
@@ -1007,7 +1088,7 @@ class HirschbergSA(_Aligner):
     ALGO = SA_HIRSCHBERG
 
 
-class GlobalGotohSA(_Aligner):
+class GlobalGotohSA(_Aligner, _BandedAffine):
     ALGO = SA_GLOBAL_GOTOH
 
 

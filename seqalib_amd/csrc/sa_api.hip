@@ -2344,6 +2344,8 @@ int sa_score_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
 // variant (cells per lane R, lanes per pair L) its clipped band fits; the pairs of one variant are
 // launched together, longest first, in as many launches as sa_set_workspace_limit leaves room for
 // their records.  A score call stores no records and launches no walk.
+// sa_align_batch_banded_affine / sa_score_batch_banded_affine (kernels: sa_banded_affine.hip) run the
+// same batching with their own checks, the first kBandAffineVariants variants and 4-bit records.
 
 // Algorithm, scoring and band checks shared with sa_banded_plan_query (c may be NULL).
 static int banded_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, uint32_t band) {
@@ -2358,11 +2360,39 @@ static int banded_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, uint32_t 
     return SA_OK;
 }
 
+// The same for sa_align_batch_banded_affine / sa_score_batch_banded_affine / sa_banded_affine_plan_query.
+static int banded_affine_prologue(sa_ctx* c, int algo, const sa_scoring* sc, uint32_t band) {
+    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
+    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
+    if (algo != SA_LOCAL_GOTOH && algo != SA_GLOBAL_GOTOH)
+        return fail(c, SA_ERR_UNSUPPORTED, "banded affine calls support SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH only");
+    if (sc->gap_extend > 0)
+        return fail(c, SA_ERR_UNSUPPORTED, "banded affine calls need gap_extend <= 0 (the records decide the walk only then)");
+    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: |n - m| + 2 * band + 1 diagonals overflow 32 bits");
+    if (band == 0 && !sc->allow_mismatch)
+        return fail(c, SA_ERR_UNSUPPORTED, "band = 0 needs allow_mismatch (a one-diagonal band has no other candidate)");
+    return SA_OK;
+}
+
 // One pair's geometry and fill variant, or why the banded path does not take it.
 static int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t m, uint64_t n, uint32_t band,
                             BandGeom* g, int* variant) {
     if (m >= (1u << 24) || n >= (1u << 24)) return fail(c, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
     auto a = [](int32_t x) { return (int64_t)(x < 0 ? -(int64_t)x : x); };
+    if (algo == SA_LOCAL_GOTOH || algo == SA_GLOBAL_GOTOH) {   // (the linear calls never get here with these)
+        const int64_t big = std::max(std::max(a(sc->gap_open) + a(sc->gap_extend), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
+        if ((int64_t)(m + n + 1) * big + 10000 >= kBandScoreLimit)
+            return fail(c, SA_ERR_UNSUPPORTED,
+                        "banded affine calls need (m + n + 1) * max(|gap_open| + |gap_extend|, |match|, |mismatch|) + 10000 < 2^29");
+        *g = band_geom((int32_t)m, (int32_t)n, (int32_t)std::min(band, kBandMaxW));
+        *variant = band_affine_variant(g->beff);
+        if (*variant < 0)
+            return fail(c, SA_ERR_UNSUPPORTED, "band of " + std::to_string(g->beff) + " diagonals inside the matrix exceeds the " +
+                                                   std::to_string(kBandAffineMaxDiagonals) + " one wave holds with three values per cell");
+        if (algo == SA_LOCAL_GOTOH && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
+            return fail(c, SA_ERR_UNSUPPORTED, "banded LocalGotoh needs (m + 1) * band diagonals < 2^31");
+        return SA_OK;
+    }
     const int64_t big = std::max(std::max(a(sc->gap), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
     if ((int64_t)(m + n + 1) * big >= kBandScoreLimit)
         return fail(c, SA_ERR_UNSUPPORTED, "banded calls need (m + n + 1) * max(|gap|, |match|, |mismatch|) < 2^29");
@@ -2378,10 +2408,20 @@ static int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t 
 
 static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                         const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                        sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
+                        sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb, bool affine = false) {
     // (the checks that need no context come first, so they answer without a device too)
-    int rc = banded_prologue(c, &algo, sc, band);
+    int rc = affine ? banded_affine_prologue(c, algo, sc, band) : banded_prologue(c, &algo, sc, band);
     if (rc) return rc;
+    const int nvariants = affine ? kBandAffineVariants : kBandVariants;
+    auto rec_words = [&](const BandGeom& g, int v) { return affine ? band_affine_rec_words(g, v) : band_rec_words(g, v); };
+    if (affine && off1 && off2) {   // the affine calls' per-pair limits answer without a context as well
+        for (uint32_t p = 0; p < npairs; ++p) {
+            if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
+            BandGeom g;
+            int v = 0;
+            if ((rc = banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, &g, &v))) return rc;
+        }
+    }
     if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
     if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
     if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
@@ -2403,7 +2443,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         BandGeom g;
         int v = 0;
         if ((rc = banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, &g, &v))) return rc;
-        words[p] = notb ? 0 : band_rec_words(g, v);
+        words[p] = notb ? 0 : rec_words(g, v);
         bucket[v].push_back(p);
     }
     // A launch of fewer waves than the device has SIMDs runs as long as one wave does, so two such
@@ -2421,7 +2461,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
         const uint64_t simds = 4ull * (uint64_t)cus;
         bool took_in = false;   // bucket[v] holds pairs moved up from v - 1
-        for (int v = 0; v + 1 < kBandVariants; ++v) {
+        for (int v = 0; v + 1 < nvariants; ++v) {
             const bool fixed = took_in;
             took_in = false;
             if (fixed || bucket[v].empty() || bucket[v + 1].empty()) continue;
@@ -2432,7 +2472,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
             for (size_t k = 0; k < bucket[v].size() && !notb && fits; ++k) {
                 const uint32_t p = bucket[v][k];
                 const BandGeom g = band_geom((int32_t)(off1[p + 1] - off1[p]), (int32_t)(off2[p + 1] - off2[p]), (int32_t)w);
-                moved[k] = band_rec_words(g, v + 1);
+                moved[k] = rec_words(g, v + 1);
                 fits = moved[k] <= budget_words;
             }
             if (!fits) continue;
@@ -2452,7 +2492,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     recoff.reserve(npairs);
     uint64_t ws_words = 0;
     int top_v = 0;
-    for (int v = 0; v < kBandVariants; ++v) {
+    for (int v = 0; v < nvariants; ++v) {
         std::vector<uint32_t>& b = bucket[v];
         if (b.empty()) continue;
         top_v = v;
@@ -2553,13 +2593,19 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         bp.allow = sc->allow_mismatch;
         bp.R = kBandR[ln.v];
         bp.L = kBandL[ln.v];
+        BandAffineParams ap;
+        static_cast<BandParams&>(ap) = bp;
+        ap.gap_open = sc->gap_open;
+        ap.gap_extend = sc->gap_extend;
         SA_HIP(c, hipEventRecord(ev[0], st));
         if (kev) SA_HIP(c, hipEventRecord(kev[0], st));
-        SA_HIP(c, launch_banded_fill(algo, ln.v, use_lut, !notb, bp, st));
+        if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, use_lut, !notb, ap, st));
+        else SA_HIP(c, launch_banded_fill(algo, ln.v, use_lut, !notb, bp, st));
         if (kev) SA_HIP(c, hipEventRecord(kev[1], st));
         SA_HIP(c, hipEventRecord(ev[1], st));
         if (!notb) {
-            SA_HIP(c, launch_banded_tb(algo, use_lut, bp, st));
+            if (affine) SA_HIP(c, launch_banded_affine_tb(algo, use_lut, ap, st));
+            else SA_HIP(c, launch_banded_tb(algo, use_lut, bp, st));
             c->tb_kernels++;
         }
         SA_HIP(c, hipEventRecord(ev[2], st));
@@ -2570,7 +2616,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     c->var_kernel[0] = SA_KERNEL_BANDED;
     c->var_R[0] = kBandR[top_v];
     c->var_W[0] = 1;
-    c->var_records[0] = notb ? SA_RECORDS_NONE : SA_RECORDS_BAND2;
+    c->var_records[0] = notb ? SA_RECORDS_NONE : affine ? SA_RECORDS_BAND4 : SA_RECORDS_BAND2;
 
     // outputs through the context's pinned staging, as the other host paths: [results][ops]
     SA_HIP(c, c->ostage.alloc(b_res + ops_total));
@@ -2613,6 +2659,33 @@ int sa_banded_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band
     if (cells_per_lane) *cells_per_lane = kBandR[v];
     if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
     if (ws_bytes_per_pair) *ws_bytes_per_pair = band_rec_words(g, v) * 4;
+    return SA_OK;
+}
+
+int sa_align_batch_banded_affine(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                                 sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, false, true);
+}
+
+int sa_score_batch_banded_affine(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                                 sa_result* results) {
+    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, nullptr, 0, true, true);
+}
+
+int sa_banded_affine_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs, int* cells_per_lane,
+                                int* pairs_per_wave, uint64_t* ws_bytes_per_pair) {
+    (void)npairs;
+    const sa_scoring any{0, 0, 0, 0, 0, 1};   // (as sa_banded_plan_query: the scoring-dependent checks are the calls')
+    int rc = banded_affine_prologue(nullptr, algo, &any, band);
+    if (rc) return rc;
+    BandGeom g;
+    int v = 0;
+    if ((rc = banded_pair_plan(nullptr, algo, &any, max_m, max_n, band, &g, &v))) return rc;
+    if (cells_per_lane) *cells_per_lane = kBandR[v];
+    if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
+    if (ws_bytes_per_pair) *ws_bytes_per_pair = band_affine_rec_words(g, v) * 4;
     return SA_OK;
 }
 

@@ -447,4 +447,26 @@ struct BandParams {
 };
 hipError_t launch_banded_fill(int algo, int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_tb(int algo, bool lut, const BandParams& p, hipStream_t s);
+
+// The banded affine path (sa_banded_affine.hip; sa_align_batch_banded_affine /
+// sa_score_batch_banded_affine): the first kBandAffineVariants entries of kBandR / kBandL, with three
+// int32 values per cell in registers and 4-bit records.  The list stops at the widest R whose align
+// kernel uses no scratch (profiles/banded_affine_resources.txt).
+constexpr int kBandAffineVariants = 7;
+constexpr int32_t kBandAffineMaxDiagonals = 2 * kBandR[kBandAffineVariants - 1] * kBandL[kBandAffineVariants - 1];
+inline int band_affine_variant(int32_t beff) {   // -1: wider than kBandAffineMaxDiagonals
+    const int v = band_variant(beff);
+    return v < kBandAffineVariants ? v : -1;
+}
+// 32-bit record words of a pair: 4 bits per cell slot, step-major ([step group][lane]).
+inline uint64_t band_affine_rec_words(const BandGeom& g, int v) {
+    const uint64_t steps = (uint64_t)(g.tend - g.tb) + 1;
+    const int R = kBandR[v], L = kBandL[v];
+    return R <= 8 ? (steps + 8 / R - 1) / (8 / R) * L : steps * (R / 8) * L;
+}
+struct BandAffineParams : BandParams {   // (gap is unused)
+    int32_t gap_open, gap_extend;
+};
+hipError_t launch_banded_affine_fill(int algo, int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_tb(int algo, bool lut, const BandAffineParams& p, hipStream_t s);
 }  // namespace sa

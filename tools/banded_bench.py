@@ -8,6 +8,9 @@ alternating so both see the same machine state:
   4096    1,000 x 4096^2  NW and SW at w = 16, 64, 256
   16384     200 x 16384^2 NW and SW at w = 64, 256
 
+--algos gg,lg runs the affine rows instead (GlobalGotoh / LocalGotoh, scoring (-3, -1, 1, -1), the banded
+affine calls against the full affine calls, w = 16, 64, 256 at both sizes; profiles/banded_affine_bench.json).
+
 The full side is sa_align_batch; where that call cannot hold its records it is sa_score_batch (and
 the banded side sa_score_batch_banded), which the row says.  Per row: wall time per call (host
 clock around the blocking call: median, min, max over --reps calls after --warmup), fill and walk
@@ -74,7 +77,10 @@ def stats(xs):
 
 
 def run_row(eng, algo, batch, w, reps, warmup):
-    sc = sa.ScoringSystem(-1, 1, -1)
+    affine = algo in (sa.SA_GLOBAL_GOTOH, sa.SA_LOCAL_GOTOH)
+    sc = sa.ScoringSystem(-3, -1, 1, -1) if affine else sa.ScoringSystem(-1, 1, -1)
+    align_banded = eng.align_banded_affine_packed if affine else eng.align_banded_packed
+    score_banded = eng.score_banded_affine_packed if affine else eng.score_banded_packed
     mode = "align"
     try:
         eng.align_packed(algo, sc, *batch)
@@ -86,8 +92,8 @@ def run_row(eng, algo, batch, w, reps, warmup):
 
     def banded():
         if mode == "align":
-            return eng.align_banded_packed(algo, sc, *batch, w)[0]
-        return eng.score_banded_packed(algo, sc, *batch, w)
+            return align_banded(algo, sc, *batch, w)[0]
+        return score_banded(algo, sc, *batch, w)
 
     kinds = {"banded": banded, "full": full}
     wall = {k: [] for k in kinds}
@@ -135,7 +141,8 @@ def run_row(eng, algo, batch, w, reps, warmup):
 
 
 SHAPES = {"4096": dict(npairs=1000, length=4096, ws=(16, 64, 256)),
-          "16384": dict(npairs=200, length=16384, ws=(64, 256))}
+          "16384": dict(npairs=200, length=16384, ws=(64, 256), affine_ws=(16, 64, 256))}
+ALGOS = {"nw": sa.SA_NW, "sw": sa.SA_SW, "gg": sa.SA_GLOBAL_GOTOH, "lg": sa.SA_LOCAL_GOTOH}
 
 
 def main():
@@ -150,17 +157,27 @@ def main():
     args = ap.parse_args()
     eng = sa.Engine(0)
     rows = []
+
+    def write():
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(dict(tool="tools/banded_bench.py", reps=args.reps, warmup=args.warmup, scale=args.scale, rows=rows),
+                          fh, indent=1)
+                fh.write("\n")
+
     for shape in args.shapes.split(","):
         spec = SHAPES[shape]
         npairs = max(1, int(round(spec["npairs"] * args.scale)))
         for alpha in args.alphabets.split(","):
             batch = related_batch(99, npairs, spec["length"], ACGT if alpha == "dna" else AA)
             for an in args.algos.split(","):
-                algo = sa.SA_NW if an == "nw" else sa.SA_SW
-                for w in spec["ws"]:
+                algo = ALGOS[an]
+                for w in (spec.get("affine_ws", spec["ws"]) if an in ("gg", "lg") else spec["ws"]):
                     doc = run_row(eng, algo, batch, w, args.reps, args.warmup)
                     doc.update(shape=f"{npairs} x {spec['length']}^2", alphabet="ACGT" if alpha == "dna" else "20 letters")
                     rows.append(doc)
+                    write()   # (after every row: a long run that is cut short keeps what it measured)
                     b, f = doc["banded"], doc["full"]
                     print(f"{doc['shape']:>16s} {alpha:3s} {an} w {w:3d} B<={doc['B_max']:4d} {doc['calls']:5s}  wall ms: banded "
                           f"{b['wall']['median_ms']:8.2f} [{b['wall']['min_ms']:.2f}, {b['wall']['max_ms']:.2f}] full "
@@ -170,12 +187,7 @@ def main():
                           f"{doc['banded_fill_cells_per_s'] / 1e9:.1f} (break-even {doc['break_even_cells_per_s'] / 1e9:.1f})  "
                           f"R {b['plan']['R']}  equal {doc['scores_equal']}/{npairs}", flush=True)
     eng.close()
-    result = dict(tool="tools/banded_bench.py", reps=args.reps, warmup=args.warmup, scale=args.scale, rows=rows)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
+    write()
     return 0 if all(r["scores_not_above"] for r in rows) else 1
 
 

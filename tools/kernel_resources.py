@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register and scratch use of every fill_kernel, fill_so2_kernel and banded_fill_kernel instantiation
+"""Register and scratch use of every fill_kernel, fill_so2_kernel and banded (affine) fill kernel instantiation
 of a translation unit, from the compiler's own resource-usage remarks (no GPU needed).
 
     tools/kernel_resources.py seqalib_amd/csrc/sa_fill_sw_score.hip [more units ...] > table.txt
@@ -20,6 +20,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-devic
 NAME = re.compile(r"Function Name: _ZN2sa11fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
 FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
 BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E")
+AFFINE = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E")
 SO2 = re.compile(r"Function Name: _ZN2sa15fill_so2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
 CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
@@ -44,6 +45,12 @@ def parse(text):
         m = BANDED.search(line)
         if m:   # the banded fills (sa_banded.hip): algorithm, R, L, LUT, REC
             cur = {"banded": tuple(int(x) for x in m.groups())}
+            rows.append(cur)
+            continue
+        m = AFFINE.search(line)
+        if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, LUT, REC
+            g = tuple(int(x) for x in m.groups())
+            cur = {"banded": (3 - g[0],) + g[1:]}
             rows.append(cur)
             continue
         m = SO2.search(line)
