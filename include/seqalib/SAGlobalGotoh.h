@@ -19,7 +19,8 @@ public:
     // and getEndCells score a diagonal move with Fn(Seq1 symbol, Seq2 symbol) instead of the scoring's
     // match / mismatch; the match function still decides Entry::IsMatchingPair.  A batch may use at
     // most 64 distinct symbols and scores must fit 16 bits (std::runtime_error otherwise); an empty
-    // function returns to match / mismatch scoring.
+    // function returns to match / mismatch scoring.  The banded forms (getAlignments / getScores /
+    // getEndCells with a band) then take the banded matrix calls (sa_align_batch_banded_matrix).
     void setSubstitution(std::function<ScoreSystemType(Ty, Ty)> Fn) { BaseType::setSubstitutionFn(std::move(Fn)); }
 
     virtual AlignedSequence<Ty, Blank> getAlignment(ContainerType& Seq1, ContainerType& Seq2) {
@@ -50,7 +51,9 @@ public:
     // and memory per pair.  With band >= max(m, n) the result is getAlignments(pairs).  Needs
     // gap_extend <= 0 and at most 2048 band diagonals inside a pair's matrix.  Byte-sized symbols, or
     // batches of at most 256 distinct symbols; a band that does not fit 32 bits throws
-    // std::runtime_error, as does setSubstitution() with a band.
+    // std::runtime_error.  After setSubstitution() the banded forms go to the banded matrix calls
+    // (sa_align_batch_banded_matrix / sa_score_batch_banded_matrix): the same band with the diagonal
+    // term Fn(a, b), at most 64 distinct symbols in a batch.
     std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
                                                           size_t band) {
         std::vector<sa_result> res;

@@ -23,7 +23,8 @@ public:
     // and getEndCells score a diagonal move with Fn(Seq1 symbol, Seq2 symbol) instead of the scoring's
     // match / mismatch; the match function still decides Entry::IsMatchingPair.  A batch may use at
     // most 64 distinct symbols and scores must fit 16 bits (std::runtime_error otherwise); an empty
-    // function returns to match / mismatch scoring.  The size-hack shapes
+    // function returns to match / mismatch scoring.  The banded forms (getAlignments / getScores /
+    // getEndCells with a band) then take the banded matrix calls (sa_align_batch_banded_matrix).  The size-hack shapes
     // (314 x 288, 60 x 57, 61 x 58) are aligned as LocalGotoh like every other shape.
     void setSubstitution(std::function<ScoreSystemType(Ty, Ty)> Fn) { BaseType::setSubstitutionFn(std::move(Fn)); }
 
@@ -69,7 +70,9 @@ public:
     // shapes are aligned as LocalGotoh like every other shape, so with band >= max(m, n) the result is
     // getAlignments(pairs) for every other shape.  Needs gap_extend <= 0 and at most 2048 band diagonals
     // inside a pair's matrix.  Byte-sized symbols, or batches of at most 256 distinct symbols; a band
-    // that does not fit 32 bits throws std::runtime_error, as does setSubstitution() with a band.
+    // that does not fit 32 bits throws std::runtime_error.  After setSubstitution() the banded forms go
+    // to the banded matrix calls (sa_align_batch_banded_matrix / sa_score_batch_banded_matrix): the
+    // same band with the diagonal term Fn(a, b), at most 64 distinct symbols in a batch.
     std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
                                                           size_t band) {
         std::vector<sa_result> res;

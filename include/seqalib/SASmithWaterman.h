@@ -30,7 +30,8 @@ public:
     // and getEndCells score a diagonal move with Fn(Seq1 symbol, Seq2 symbol) instead of the scoring's
     // match / mismatch; the match function still decides Entry::IsMatchingPair.  A batch may use at
     // most 64 distinct symbols and scores must fit 16 bits (std::runtime_error otherwise); an empty
-    // function returns to match / mismatch scoring.
+    // function returns to match / mismatch scoring.  The banded forms (getAlignments / getScores /
+    // getEndCells with a band) then take the banded matrix calls (sa_align_batch_banded_matrix).
     void setSubstitution(std::function<ScoreSystemType(Ty, Ty)> Fn) { BaseType::setSubstitutionFn(std::move(Fn)); }
 
     virtual AlignedSequence<Ty, Blank> getAlignment(ContainerType& Seq1, ContainerType& Seq2) {

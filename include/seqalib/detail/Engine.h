@@ -430,7 +430,8 @@ using ChunkFn = std::function<void(size_t, size_t)>;
 inline void chunk_tramp(void* user, uint32_t p0, uint32_t p1) { (*static_cast<ChunkFn*>(user))(p0, p1); }
 
 // sub: the aligner's setSubstitution() function, or NULL; with one the batch takes the matrix call
-// (one range, this thread's context, no band; fn then only labels matching pairs).
+// (one range, this thread's context; fn then only labels matching pairs), with a band the banded
+// matrix call (sa_align_batch_banded_matrix / sa_score_batch_banded_matrix).
 template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubFnTy = std::function<int(Ty, Ty)>>
 void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
@@ -444,7 +445,6 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     raw_vector<uint8_t>&s1 = *pk.s1, &s2 = *pk.s2;
     tm.lap("symbol coding");
     if (sub) {
-        if (band != kNoBand) throw std::runtime_error("seqalib: substitution scoring has no banded call");
         const std::vector<int16_t> tab = build_submat(coder, *sub);
         std::vector<uint8_t> mlut;
         if (has_fn) mlut = build_lut(coder, fn);
@@ -455,10 +455,17 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
         ops_off.resize(n);
         for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
         tm.lap("score table + buffers");
-        check(sa_align_batch_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
-                                    has_fn ? mlut.data() : nullptr, res.data(), ops.data(), cap),
-              "sa_align_batch_matrix");
-        tm.lap("sa_align_batch_matrix (GPU)");
+        if (band != kNoBand) {
+            check(sa_align_batch_banded_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
+                                               has_fn ? mlut.data() : nullptr, band_arg(band), res.data(), ops.data(), cap),
+                  "sa_align_batch_banded_matrix");
+            tm.lap("sa_align_batch_banded_matrix (GPU)");
+        } else {
+            check(sa_align_batch_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
+                                        has_fn ? mlut.data() : nullptr, res.data(), ops.data(), cap),
+                  "sa_align_batch_matrix");
+            tm.lap("sa_align_batch_matrix (GPU)");
+        }
         if (on_chunk && n) on_chunk(0, n);
         for (auto& r : res)
             if (r.flags & SA_FLAG_DIVERGED)
@@ -527,14 +534,20 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     const uint32_t n = (uint32_t)pairs.size();
     res.assign(n, sa_result{});
     if (sub) {
-        if (band != kNoBand) throw std::runtime_error("seqalib: substitution scoring has no banded call");
         const std::vector<int16_t> tab = build_submat(coder, *sub);
         std::vector<uint8_t> mlut;
         if (has_fn) mlut = build_lut(coder, fn);
-        check(sa_score_batch_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
-                                    has_fn ? mlut.data() : nullptr, res.data()),
-              "sa_score_batch_matrix");
-        tm.lap("sa_score_batch_matrix (GPU)");
+        if (band != kNoBand) {
+            check(sa_score_batch_banded_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
+                                               has_fn ? mlut.data() : nullptr, band_arg(band), res.data()),
+                  "sa_score_batch_banded_matrix");
+            tm.lap("sa_score_batch_banded_matrix (GPU)");
+        } else {
+            check(sa_score_batch_matrix(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, tab.data(),
+                                        has_fn ? mlut.data() : nullptr, res.data()),
+                  "sa_score_batch_matrix");
+            tm.lap("sa_score_batch_matrix (GPU)");
+        }
     } else if (band != kNoBand) {
         banded_needs_table(coder.overflow);
         std::vector<uint8_t> lut;

@@ -384,6 +384,53 @@ int sa_matrix_plan_query(int algo, const sa_scoring* scoring, uint32_t max_m, ui
                          uint32_t npairs, int nsym, int* kernel, int* rows_per_lane, int* waves,
                          uint64_t* workspace_bytes_per_pair);
 
+/* Banded substitution-matrix scoring: the band of sa_align_batch_banded (SA_SW, SA_NW: 2-bit records,
+ * up to 4096 band diagonals inside the matrix) or of sa_align_batch_banded_affine (SA_LOCAL_GOTOH,
+ * SA_GLOBAL_GOTOH: 4-bit records, up to 2048) with the diagonal term of sa_align_batch_matrix.
+ * Band geometry, the rule that a term which would read a cell outside the band is no candidate,
+ * borders, tie order, the end-cell rule, traceback order and op codes are those banded calls'; the
+ * only change is the diagonal term, (match(a, b) ? match : mismatch) replaced by submat[a * 256 + b].
+ * scoring->match, mismatch and allow_mismatch are ignored: mismatches are always allowed, so band == 0
+ * is valid for every scoring and 'X' never appears.  gap (linear) or gap_open / gap_extend (affine) are
+ * read.  A diagonal op is 'M' when match_lut says the two symbols match (NULL: byte equality), else
+ * 'S'; match_lut labels ops only, it changes no score.
+ * This is the raw path: the LocalGotoh size hack is never applied and flags = 0.
+ * Score call: start = (-1, -1), nops = 0, reserved = 0, flags = 0; no records, no walk,
+ * traceback_ms == 0.
+ * With band >= max(m, n) every result field and op equals sa_align_batch_matrix's, for scorings where
+ * that call sets no flag; for any band the score is <= the unbanded matrix score.  Empty inputs give
+ * what the banded calls without a table give.
+ * Status codes (these checks are made before the context is looked at, so they give the same status
+ * with a NULL context; a NULL context with valid arguments: SA_ERR_ARG):
+ *   NULL scoring, NULL submat, an invalid algo, band >= 2^31, bad offsets or buffers: SA_ERR_ARG.
+ *   SA_HIRSCHBERG, SA_MYERS_MILLER: SA_ERR_UNSUPPORTED, as in the matrix calls.
+ *   An affine algo with gap_extend > 0: SA_ERR_UNSUPPORTED (gap_open may have any sign).
+ *   More than 64 distinct symbols in the batch, both sequence sets together: SA_ERR_UNSUPPORTED.
+ *   SA_ERR_UNSUPPORTED also for a pair with
+ *     a sequence of >= 2^24 symbols,
+ *     linear: (m + n + 1) * max(|gap|, max |S|) >= 2^29,
+ *     affine: (m + n + 1) * max(|gap_open| + |gap_extend|, max |S|) + 10000 >= 2^29 (the banded affine
+ *       calls' bound, stricter than sa_align_batch_matrix's),
+ *     more than 4096 (linear) or 2048 (affine) band diagonals inside its matrix,
+ *     SA_SW / SA_LOCAL_GOTOH: (m + 1) * that number of diagonals >= 2^31,
+ *   where max |S| runs over the symbol pairs of the batch.
+ *   ops_cap too small: SA_ERR_CAPACITY.  One pair's records above the workspace limit: SA_ERR_NOMEM.
+ * There is no plan query of its own: a pair's variant and workspace are what sa_banded_plan_query
+ * (SA_SW, SA_NW) or sa_banded_affine_plan_query (SA_LOCAL_GOTOH, SA_GLOBAL_GOTOH) report for the same
+ * shape and band.  sa_last_timings works after either call; sa_last_plan_ex reports SA_KERNEL_BANDED,
+ * the cells per lane and step of the widest variant the call used, 1 wave, and SA_RECORDS_BAND2 /
+ * SA_RECORDS_BAND4 / SA_RECORDS_NONE. */
+int sa_align_batch_banded_matrix(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const int16_t* submat, const uint8_t* match_lut, uint32_t band,
+                                 sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_banded_matrix(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const int16_t* submat, const uint8_t* match_lut, uint32_t band,
+                                 sa_result* results);
+
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events
  * recorded on the stream they ran on: total fill-kernel ms, total traceback-kernel ms, and the
  * number of fill launches.  Waits for those events. */

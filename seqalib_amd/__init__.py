@@ -153,6 +153,10 @@ def load_library():
     L.sa_score_batch_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.sa_matrix_plan_query.argtypes = [C.c_int, C.POINTER(_Scoring), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                        i32p, i32p, i32p, u64p]
+    L.sa_align_batch_banded_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
+                                               C.c_uint32, vp, vp, C.c_uint64]
+    L.sa_score_batch_banded_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
+                                               C.c_uint32, vp]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
     L.sa_last_kernel_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sa_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p, u64p]
@@ -173,6 +177,7 @@ def load_library():
                "sa_align_batch_banded", "sa_score_batch_banded", "sa_banded_plan_query",
                "sa_align_batch_banded_affine", "sa_score_batch_banded_affine", "sa_banded_affine_plan_query",
                "sa_align_batch_matrix", "sa_score_batch_matrix", "sa_matrix_plan_query",
+               "sa_align_batch_banded_matrix", "sa_score_batch_banded_matrix",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -670,6 +675,67 @@ class Engine:
         s1, off1, s2, off2 = pack_pairs(pairs)
         return self._score_results(self.score_matrix_packed(algo, scoring, s1, off1, s2, off2, matrix, lut))
 
+    def align_banded_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, matrix, band: int,
+                                   lut: Optional[np.ndarray] = None):
+        """Banded substitution-matrix host-buffer batch (sa_align_batch_banded_matrix): the band of
+        align_banded_packed (SW / NW) or align_banded_affine_packed (LocalGotoh / GlobalGotoh) with the
+        diagonal term matrix[a, b]; only the gap terms of `scoring` are read; `lut` labels diagonal ops
+        'M' / 'S'.  Returns (results, ops) as align_packed."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        tab = _submat_arg(matrix)
+        ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        ops = np.zeros(ops_cap, dtype=np.uint8)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_align_batch_banded_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                                 npairs, _ptr(tab), lut_p, _band_arg(band), _ptr(res), _ptr(ops), ops_cap)
+        self._check(rc, "sa_align_batch_banded_matrix")
+        return res[:npairs], ops
+
+    def score_banded_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, matrix, band: int,
+                                   lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Banded substitution-matrix score batch (sa_score_batch_banded_matrix): the results array
+        (start = -1, nops = 0)."""
+        npairs = len(off1) - 1
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
+        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
+        tab = _submat_arg(matrix)
+        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
+        lut_p = 0
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+            lut_p = _ptr(lut)
+        sc = scoring._c()
+        rc = self.L.sa_score_batch_banded_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
+                                                 npairs, _ptr(tab), lut_p, _band_arg(band), _ptr(res))
+        self._check(rc, "sa_score_batch_banded_matrix")
+        return res[:npairs]
+
+    def align_banded_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
+                            band: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the banded matrix call."""
+        def call(algo, scoring, s1, off1, s2, off2, band, lut):
+            return self.align_banded_matrix_packed(algo, scoring, s1, off1, s2, off2, matrix, band, lut)
+        return self._align_banded_pairs(call, algo, scoring, pairs, band, lut)
+
+    def score_banded_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
+                            band: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the banded matrix call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_banded_matrix_packed(algo, scoring, s1, off1, s2, off2, matrix, band, lut))
+
     def align_bits(self, algo: int, scoring: ScoringSystem, off1: np.ndarray, off2: np.ndarray, bits: np.ndarray,
                    bits_off: np.ndarray):
         """Generic-Ty batch (sa_align_batch_bits) from match_bitmaps(): (results, ops)."""
@@ -983,7 +1049,7 @@ class _Aligner:
         eng = _engine(self.device)
         if self.matrix is not None:
             if band is not None:
-                raise SeqalibError("a substitution matrix and band= cannot be combined")
+                raise SeqalibError("a substitution matrix and band= cannot be combined here: use getBandedMatrixAlignments / getBandedMatrixScores")
             res = eng.align_matrix(self.ALGO, self.scoring, pairs, self.matrix, self._lut(pairs))
         elif band is None:
             res = eng.align(self.ALGO, self.scoring, pairs, self._lut(pairs))
@@ -1009,7 +1075,7 @@ class _Aligner:
     def _score_results(self, pairs, band: Optional[int] = None) -> List[PairResult]:
         if self.matrix is not None:
             if band is not None:
-                raise SeqalibError("a substitution matrix and band= cannot be combined")
+                raise SeqalibError("a substitution matrix and band= cannot be combined here: use getBandedMatrixAlignments / getBandedMatrixScores")
             res = _engine(self.device).score_matrix(self.ALGO, self.scoring, pairs, self.matrix, self._lut(pairs))
         elif band is None:
             res = _engine(self.device).score(self.ALGO, self.scoring, pairs, self._lut(pairs))
@@ -1034,14 +1100,49 @@ class _LocalAligner(_Aligner):
         return [(r.end_i, r.end_j) for r in self._score_results(pairs, band)]
 
 
+class _BandedMatrix:
+    """The banded matrix calls (sa_align_batch_banded_matrix) on the four classes that take a
+    substitution matrix.  They are separate methods because band= on getAlignments / getScores and
+    getBanded* keep raising on an aligner built with matrix=.  Results are the raw path's (no
+    LocalGotoh size hack)."""
+
+    def _banded_matrix_check(self):
+        if self.matrix is None:
+            raise SeqalibError("getBandedMatrix* need an aligner built with matrix=")
+
+    def getBandedMatrixAlignments(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[AlignedSequence]:
+        self._banded_matrix_check()
+        res = _engine(self.device).align_banded_matrix(self.ALGO, self.scoring, pairs, self.matrix, band, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return [expand_ops(self.ALGO, a, b, r, self.blank) for (a, b), r in zip(pairs, res)]
+
+    def getBandedMatrixAlignment(self, seq1, seq2, band: int) -> AlignedSequence:
+        return self.getBandedMatrixAlignments([(seq1, seq2)], band)[0]
+
+    def _banded_matrix_score_results(self, pairs, band: int) -> List[PairResult]:
+        self._banded_matrix_check()
+        res = _engine(self.device).score_banded_matrix(self.ALGO, self.scoring, pairs, self.matrix, band, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return res
+
+    def getBandedMatrixScores(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[int]:
+        return [r.score for r in self._banded_matrix_score_results(pairs, band)]
+
+
+class _BandedMatrixLocal(_BandedMatrix):
+    def getBandedMatrixEndCells(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[Tuple[int, int]]:
+        """(MaxRow, MaxCol) of every pair: the last in-band row-major cell holding the maximum."""
+        return [(r.end_i, r.end_j) for r in self._banded_matrix_score_results(pairs, band)]
+
+
 class _BandedAffine:
     """The banded affine calls on LocalGotohSA / GlobalGotohSA.  They are separate methods because
     band= on getAlignments / getScores keeps raising for these classes.  Results are the raw path's
-    (no LocalGotoh size hack); a substitution matrix cannot be combined with a band."""
+    (no LocalGotoh size hack); with a substitution matrix the banded form is getBandedMatrix*."""
 
     def _banded_affine_check(self):
         if self.matrix is not None:
-            raise SeqalibError("a substitution matrix and a band cannot be combined")
+            raise SeqalibError("a substitution matrix and a band cannot be combined here: use getBandedMatrixAlignments / getBandedMatrixScores")
 
     def getBandedAlignments(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[AlignedSequence]:
         self._banded_affine_check()
@@ -1062,7 +1163,7 @@ class _BandedAffine:
         return [r.score for r in self._banded_score_results(pairs, band)]
 
 
-class SmithWatermanSA(_LocalAligner):
+class SmithWatermanSA(_LocalAligner, _BandedMatrixLocal):
     ALGO = SA_SW
 
     @staticmethod
@@ -1070,11 +1171,11 @@ class SmithWatermanSA(_LocalAligner):
         return ScoringSystem(-1, 1, -1)   # SASmithWaterman.h:352
 
 
-class NeedlemanWunschSA(_Aligner):
+class NeedlemanWunschSA(_Aligner, _BandedMatrix):
     ALGO = SA_NW
 
 
-class LocalGotohSA(_LocalAligner, _BandedAffine):
+class LocalGotohSA(_LocalAligner, _BandedAffine, _BandedMatrixLocal):
     ALGO = SA_LOCAL_GOTOH
 
     def getBandedEndCells(self, pairs: Sequence[Tuple[object, object]], band: int) -> List[Tuple[int, int]]:
@@ -1088,7 +1189,7 @@ class HirschbergSA(_Aligner):
     ALGO = SA_HIRSCHBERG
 
 
-class GlobalGotohSA(_Aligner, _BandedAffine):
+class GlobalGotohSA(_Aligner, _BandedAffine, _BandedMatrix):
     ALGO = SA_GLOBAL_GOTOH
 
 

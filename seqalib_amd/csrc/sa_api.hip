@@ -2346,6 +2346,8 @@ int sa_score_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
 // their records.  A score call stores no records and launches no walk.
 // sa_align_batch_banded_affine / sa_score_batch_banded_affine (kernels: sa_banded_affine.hip) run the
 // same batching with their own checks, the first kBandAffineVariants variants and 4-bit records.
+// sa_align_batch_banded_matrix / sa_score_batch_banded_matrix (banded_matrix_batch, below the matrix
+// calls) run it too, linear or affine by algorithm, on recoded sequences with the kMatchSub fills.
 
 // Algorithm, scoring and band checks shared with sa_banded_plan_query (c may be NULL).
 static int banded_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, uint32_t band) {
@@ -2406,15 +2408,28 @@ static int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t 
     return SA_OK;
 }
 
+// A matrix band call's recode (banded_matrix_batch): the batch's K used symbols in byte order, their
+// codes, and the used K x K corner of the caller's table, dense (row stride K; K >= 1).
+struct BandSub {
+    uint8_t code[256];
+    int syms[kSubMaxSyms];
+    int K;
+    std::vector<int16_t> tab;   // kSubMaxSyms^2 entries, the first K * K used
+};
+
+// sub (the matrix band calls): the caller has run the algorithm, scoring and buffer checks, *sc holds
+// the table's extremes as match / mismatch with allow_mismatch = 1 (what banded_pair_plan bounds the
+// scores by), lut only labels, and the sequences are recoded on their way to the device.
 static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                         const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                        sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb, bool affine = false) {
+                        sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb, bool affine = false,
+                        const BandSub* sub = nullptr) {
     // (the checks that need no context come first, so they answer without a device too)
-    int rc = affine ? banded_affine_prologue(c, algo, sc, band) : banded_prologue(c, &algo, sc, band);
+    int rc = sub ? SA_OK : affine ? banded_affine_prologue(c, algo, sc, band) : banded_prologue(c, &algo, sc, band);
     if (rc) return rc;
     const int nvariants = affine ? kBandAffineVariants : kBandVariants;
     auto rec_words = [&](const BandGeom& g, int v) { return affine ? band_affine_rec_words(g, v) : band_rec_words(g, v); };
-    if (affine && off1 && off2) {   // the affine calls' per-pair limits answer without a context as well
+    if ((affine || sub) && off1 && off2) {   // the affine and matrix calls' per-pair limits answer without a context as well
         for (uint32_t p = 0; p < npairs; ++p) {
             if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
             BandGeom g;
@@ -2524,14 +2539,21 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     std::vector<uint32_t> bits;
     if (use_lut) {
         bits.assign(2048, 0);
-        for (int a = 0; a < 256; ++a)
-            for (int b = 0; b < 256; ++b)
-                if (lut[a * 256 + b]) bits[a * 8 + b / 32] |= 1u << (b % 32);
+        if (sub) {   // the walk reads codes: the label table over codes (equality of codes is equality of bytes)
+            for (int a = 0; a < sub->K; ++a)
+                for (int b = 0; b < sub->K; ++b)
+                    if (lut[sub->syms[a] * 256 + sub->syms[b]]) bits[a * 8 + b / 32] |= 1u << (b % 32);
+        } else {
+            for (int a = 0; a < 256; ++a)
+                for (int b = 0; b < 256; ++b)
+                    if (lut[a * 256 + b]) bits[a * 8 + b / 32] |= 1u << (b % 32);
+        }
     }
     auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
     const uint64_t b_s1 = al(t1 + 1), b_s2 = al(t2 + 1), b_o = al(8ull * (npairs + 1)), b_res = al(sizeof(sa_result) * (uint64_t)npairs);
     const uint64_t b_ops = al(ops_total + 1), b_bits = al(8192), b_idx = al(4ull * npairs), b_ro = al(8ull * npairs);
-    if ((rc = ensure_io(c, b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_bits + b_idx + b_ro))) return rc;
+    const uint64_t b_tab = sub ? al(2ull * kSubMaxSyms * kSubMaxSyms) : 0;
+    if ((rc = ensure_io(c, b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_bits + b_idx + b_ro + b_tab))) return rc;
     uint8_t* q = c->io;
     uint8_t* const d1 = q; q += b_s1;
     uint8_t* const d2 = q; q += b_s2;
@@ -2541,10 +2563,24 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     uint8_t* const dops = q; q += b_ops;
     uint32_t* const dbits = reinterpret_cast<uint32_t*>(q); q += b_bits;
     uint32_t* const didx = reinterpret_cast<uint32_t*>(q); q += b_idx;
-    uint64_t* const dro = reinterpret_cast<uint64_t*>(q);
+    uint64_t* const dro = reinterpret_cast<uint64_t*>(q); q += b_ro;
+    int16_t* const dtab = reinterpret_cast<int16_t*>(q);
     hipStream_t st = c->stream;
-    if (t1) SA_HIP(c, hipMemcpyAsync(d1, seq1, t1, hipMemcpyHostToDevice, st));
-    if (t2) SA_HIP(c, hipMemcpyAsync(d2, seq2, t2, hipMemcpyHostToDevice, st));
+    if (sub) {   // pinned staging: [Seq1 codes][Seq2 codes][table]
+        SA_HIP(c, c->stage.alloc(b_s1 + b_s2 + b_tab));
+        uint8_t* const h1 = c->stage.data();
+        uint8_t* const h2 = h1 + b_s1;
+        const uint8_t* const code = sub->code;
+        par_for(t1, 1u << 20, [&](uint64_t lo, uint64_t hi) { for (uint64_t k = lo; k < hi; ++k) h1[k] = code[seq1[k]]; });
+        par_for(t2, 1u << 20, [&](uint64_t lo, uint64_t hi) { for (uint64_t k = lo; k < hi; ++k) h2[k] = code[seq2[k]]; });
+        memcpy(h2 + b_s2, sub->tab.data(), 2ull * kSubMaxSyms * kSubMaxSyms);
+        if (t1) SA_HIP(c, hipMemcpyAsync(d1, h1, t1, hipMemcpyHostToDevice, st));
+        if (t2) SA_HIP(c, hipMemcpyAsync(d2, h2, t2, hipMemcpyHostToDevice, st));
+        SA_HIP(c, hipMemcpyAsync(dtab, h2 + b_s2, 2ull * kSubMaxSyms * kSubMaxSyms, hipMemcpyHostToDevice, st));
+    } else {
+        if (t1) SA_HIP(c, hipMemcpyAsync(d1, seq1, t1, hipMemcpyHostToDevice, st));
+        if (t2) SA_HIP(c, hipMemcpyAsync(d2, seq2, t2, hipMemcpyHostToDevice, st));
+    }
     SA_HIP(c, hipMemcpyAsync(do1, off1, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
     SA_HIP(c, hipMemcpyAsync(do2, off2, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
     if (use_lut) SA_HIP(c, hipMemcpyAsync(dbits, bits.data(), 8192, hipMemcpyHostToDevice, st));
@@ -2556,6 +2592,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     c->kvars.clear();
     c->timed_stream = st;
     c->tb_kernels = 0;
+    const int mm = sub ? kMatchSub : use_lut ? kMatchLut : kMatchEq;
     for (const Launch& ln : launches) {
         while ((int)c->events.size() < 3 * (c->launches + 1)) {
             hipEvent_t ev;
@@ -2593,14 +2630,16 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         bp.allow = sc->allow_mismatch;
         bp.R = kBandR[ln.v];
         bp.L = kBandL[ln.v];
+        bp.submat = sub ? dtab : nullptr;
+        bp.sub_k = sub ? (uint32_t)sub->K : 0;
         BandAffineParams ap;
         static_cast<BandParams&>(ap) = bp;
         ap.gap_open = sc->gap_open;
         ap.gap_extend = sc->gap_extend;
         SA_HIP(c, hipEventRecord(ev[0], st));
         if (kev) SA_HIP(c, hipEventRecord(kev[0], st));
-        if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, use_lut, !notb, ap, st));
-        else SA_HIP(c, launch_banded_fill(algo, ln.v, use_lut, !notb, bp, st));
+        if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, mm, !notb, ap, st));
+        else SA_HIP(c, launch_banded_fill(algo, ln.v, mm, !notb, bp, st));
         if (kev) SA_HIP(c, hipEventRecord(kev[1], st));
         SA_HIP(c, hipEventRecord(ev[1], st));
         if (!notb) {
@@ -2859,6 +2898,75 @@ int sa_score_batch_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
                           const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
                           const uint8_t* match_lut, sa_result* results) {
     return matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, results, nullptr, 0, true);
+}
+
+// sa_align_batch_banded_matrix / sa_score_batch_banded_matrix: the symbol scan, codes and dense table of
+// matrix_batch, then banded_batch (linear or affine by algorithm) with the kMatchSub fills.  The
+// per-pair score bounds are the banded calls' own, with the table's extremes in place of match /
+// mismatch -- for the affine algorithms the stricter |gap_open| + |gap_extend| form, which the
+// sentinel argument of the affine band needs.
+static int banded_matrix_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                               const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
+                               const uint8_t* lut, uint32_t band, sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
+    // (the checks that need no context come first, so they answer without a device too)
+    int rc = matrix_prologue(c, algo, sc);
+    if (rc) return rc;
+    const bool affine = is_affine(algo);
+    if (affine && sc->gap_extend > 0)
+        return fail(c, SA_ERR_UNSUPPORTED, "banded affine calls need gap_extend <= 0 (the records decide the walk only then)");
+    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: |n - m| + 2 * band + 1 diagonals overflow 32 bits");
+    if (!submat) return fail(c, SA_ERR_ARG, "submat is NULL");
+    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
+    if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
+    if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
+    for (uint32_t p = 0; p < npairs; ++p)
+        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
+    const uint64_t t1 = off1[npairs], t2 = off2[npairs];
+
+    // the batch's symbols, both sides together: codes in byte order (as matrix_batch)
+    BandSub sub;
+    bool seen[256] = {};
+    for (uint64_t k = 0; k < t1; ++k) seen[seq1[k]] = true;
+    for (uint64_t k = 0; k < t2; ++k) seen[seq2[k]] = true;
+    memset(sub.code, 0, sizeof(sub.code));
+    int K = 0;
+    for (int b = 0; b < 256; ++b)
+        if (seen[b]) {
+            if (K == kSubMaxSyms)
+                return fail(c, SA_ERR_UNSUPPORTED, "matrix calls take batches of at most " + std::to_string(kSubMaxSyms) +
+                                                       " distinct symbols (both sequence sets together)");
+            sub.code[b] = (uint8_t)K;
+            sub.syms[K++] = b;
+        }
+    if (K == 0) sub.syms[K++] = 0;   // (no symbol at all: a one-entry table, so that no lane indexes outside it)
+    sub.K = K;
+    sub.tab.assign(kSubMaxSyms * kSubMaxSyms, 0);
+    int32_t smax = 0, smin = 0;
+    for (int a = 0; a < K; ++a)
+        for (int b = 0; b < K; ++b) {
+            const int16_t s = submat[sub.syms[a] * 256 + sub.syms[b]];
+            sub.tab[a * K + b] = s;
+            smax = std::max<int32_t>(smax, s);
+            smin = std::min<int32_t>(smin, s);
+        }
+    // what banded_pair_plan reads of the scoring: the diagonal term's extremes
+    sa_scoring sc2 = *sc;
+    sc2.match = smax;
+    sc2.mismatch = smin;
+    sc2.allow_mismatch = 1;
+    return banded_batch(c, algo, &sc2, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, notb, affine, &sub);
+}
+
+int sa_align_batch_banded_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
+                                 const uint8_t* match_lut, uint32_t band, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    return banded_matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, band, results, ops, ops_cap, false);
+}
+
+int sa_score_batch_banded_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
+                                 const uint8_t* match_lut, uint32_t band, sa_result* results) {
+    return banded_matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, band, results, nullptr, 0, true);
 }
 
 int sa_matrix_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,

@@ -1,0 +1,353 @@
+// sa_banded_affine_fill.h — the banded LocalGotoh / GlobalGotoh fill (sa_align_batch_banded_affine,
+// sa_score_batch_banded_affine, and the affine half of sa_align_batch_banded_matrix): the anti-diagonal
+// sweep of sa_banded_fill.h with three values per cell (M, X vertical, Y horizontal) and 4-bit records
+// laid out by anti-diagonal.  DESIGN.md §2.13, §2.14.  Instantiated by sa_banded_affine.hip (kMatchEq,
+// kMatchLut) and sa_banded_affine_sub.hip (kMatchSub); the match modes are those of sa_banded_fill.h.
+//
+// Geometry and register mapping are those of sa_banded_fill.h (BandGeom, sa_internal.h): lane l of the
+// pair's L lanes owns the 2R diagonals c = 2lR .. 2lR + 2R - 1 in an even set (EM/EX/EY[r], c = 2lR +
+// 2r) and an odd set (OM/OX/OY[r], c = 2lR + 2r + 1).  Per step:
+//   even step: left (i, j-1) = O[r-1] supplies M and Y (r = 0: lane l-1's O[R-1], two DPP wave shifts),
+//              up (i-1, j) = O[r] supplies M and X, diagonal (i-1, j-1) = EM[r] before the update;
+//   odd step:  left = E[r], up = E[r+1] (r = R-1: lane l+1's E[0], two DPP wave shifts), diagonal OM[r].
+// A cell that does not exist (outside the matrix, outside the band, c >= B') holds kBandNeg in all
+// three values.  X of a cell whose upper neighbour does not exist is max(kBandNeg + open, kBandNeg +
+// extend): below every real score (the host admits |score| + 10000 < 2^29 only, and |open| < 2^29),
+// so it is never the maximum, never equal to a real value, and one more "+ extend" on it (the cell
+// below reads it once, beside a real open term) does not wrap.  Y likewise.  That is how "a term that
+// would read a cell outside the band is no candidate" is kept without a flag per value.
+//
+// Record of a cell (4 bits): bits 0-1 the M code (0 stop: local and M = 0, 1 diagonal, 2 M = X,
+// 3 M = Y, tested in that order), bit 2 "X = X(i-1, j) + extend" (tested before the open term, as the
+// walk does), bit 3 "Y = Y(i, j-1) + extend".  With gap_extend <= 0 these decide the walk (DESIGN.md
+// §2.13): it never needs a value.
+#pragma once
+#include "sa_internal.h"
+
+namespace sa {
+namespace {
+
+constexpr int32_t kBorderXY = -10000;   // X and Y of every border cell (the reference's constant)
+
+__device__ __forceinline__ int32_t aff_from_lower_lane(int32_t v) {   // lane l takes lane l - 1's, lane 0 kBandNeg
+    return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ int32_t aff_from_upper_lane(int32_t v) {   // lane l takes lane l + 1's, lane 63 kBandNeg
+    return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x130, 0xf, 0xf, false);
+}
+
+template <bool LOCAL, int R, int L, int MM, bool REC>
+struct BandAffineFill {
+    static constexpr int S = R <= 8 ? 8 / R : 1;         // steps per record word
+    static constexpr int WPS = R <= 8 ? 1 : R / 8;       // record words per step
+    int32_t EM[R], EX[R], EY[R], OM[R], OX[R], OY[R];
+    uint32_t A[R], Bw[R + 1];
+    int32_t m, n, lo, beff, rlimE, rlimO, l;
+    int32_t goe, ge, gopen, match, mism;   // goe = gap_open + gap_extend
+    const uint32_t* lut;
+    const int16_t* sub;  // kMatchSub: the K x K table in LDS
+    long long best;      // local: (M << 32 | i * beff + c) of the last row-major maximum
+    int32_t score;       // global: M[m][n]
+    uint32_t w[WPS];     // the step's 4-bit records
+
+    // One step.  PAR: 0 even (E), 1 odd (O).  EDGE: the step may hold border cells or cells outside
+    // the matrix; otherwise every cell with c < B' is an interior cell.
+    template <int PAR, bool EDGE>
+    __device__ __forceinline__ void step(int32_t h) {
+        int32_t shM, shG;   // the neighbour lane's M and its Y (even step) / X (odd step)
+        if (PAR == 0) {
+            shM = aff_from_lower_lane(OM[R - 1]);
+            shG = aff_from_lower_lane(OY[R - 1]);
+            if (l == 0) shM = shG = kBandNeg;
+        } else {
+            shM = aff_from_upper_lane(EM[0]);
+            shG = aff_from_upper_lane(EX[0]);
+            if (l == L - 1) shM = shG = kBandNeg;
+        }
+        const int32_t i0 = h - l * R, j0 = h + l * R + lo + PAR;
+        const int32_t rlim = PAR ? rlimO : rlimE;
+        uint32_t pos = (uint32_t)i0 * (uint32_t)beff + (uint32_t)(2 * l * R + PAR);
+        const uint32_t dpos = 2u - (uint32_t)beff;
+#pragma unroll
+        for (int k = 0; k < WPS; ++k) w[k] = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int32_t leftM, leftY, upM, upX, dg;
+            uint32_t a = A[r], b;
+            if (PAR == 0) {
+                leftM = r ? OM[r > 0 ? r - 1 : 0] : shM;
+                leftY = r ? OY[r > 0 ? r - 1 : 0] : shG;
+                upM = OM[r];
+                upX = OX[r];
+                dg = EM[r];
+                b = Bw[r];
+            } else {
+                leftM = EM[r];
+                leftY = EY[r];
+                upM = r < R - 1 ? EM[r < R - 1 ? r + 1 : r] : shM;
+                upX = r < R - 1 ? EX[r < R - 1 ? r + 1 : r] : shG;
+                dg = OM[r];
+                b = Bw[r + 1];
+            }
+            int32_t cd;
+            if (MM == kMatchSub) {
+                cd = dg + sub[a + b];
+            } else {
+                bool mt;
+                if (MM == kMatchLut) mt = (lut[(a << 3) | (b >> 5)] >> (b & 31)) & 1u;
+                else mt = a == b;
+                cd = dg + (mt ? match : mism);
+            }
+            const int32_t xe = upX + ge, ye = leftY + ge;
+            const int32_t x = max(upM + goe, xe), y = max(leftM + goe, ye);
+            int32_t hv = max(max(cd, x), y);
+            if (LOCAL) hv = max(hv, 0);
+            uint32_t code = hv == cd ? 1u : hv == x ? 2u : 3u;
+            if (LOCAL && hv == 0) code = 0;
+            code |= (x == xe ? 4u : 0u) | (y == ye ? 8u : 0u);
+            const int32_t i = i0 - r, j = j0 + r;
+            const bool inb = r < rlim;
+            bool interior = inb;
+            int32_t vM, vX, vY;
+            if (EDGE) {
+                interior = inb && (uint32_t)(i - 1) < (uint32_t)m && (uint32_t)(j - 1) < (uint32_t)n;
+                const bool border = inb && ((i == 0 && (uint32_t)j <= (uint32_t)n) || (j == 0 && (uint32_t)i <= (uint32_t)m));
+                const int32_t kk = i == 0 ? j : i;
+                const int32_t bval = LOCAL || kk == 0 ? 0 : (int32_t)((uint32_t)gopen + (uint32_t)kk * (uint32_t)ge);
+                vM = interior ? hv : border ? bval : kBandNeg;
+                vX = interior ? x : border ? kBorderXY : kBandNeg;
+                vY = interior ? y : border ? kBorderXY : kBandNeg;
+                if (!LOCAL && inb && i == m && j == n) score = vM;
+            } else {
+                vM = inb ? hv : kBandNeg;
+                vX = inb ? x : kBandNeg;
+                vY = inb ? y : kBandNeg;
+            }
+            if (LOCAL) {
+                const long long key = (long long)(((unsigned long long)(uint32_t)hv << 32) | pos);
+                if (interior && key > best) best = key;
+                pos += dpos;
+            }
+            if (PAR == 0) {
+                EM[r] = vM;
+                EX[r] = vX;
+                EY[r] = vY;
+            } else {
+                OM[r] = vM;
+                OX[r] = vX;
+                OY[r] = vY;
+            }
+            if (REC) w[r / 8] |= code << (4 * (r & 7));
+        }
+    }
+};
+
+template <bool LOCAL, int R, int L, int MM, bool REC>
+__global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams P) {
+    using F = BandAffineFill<LOCAL, R, L, MM, REC>;
+    constexpr int PPW = 64 / L, S = F::S, WPS = F::WPS;
+    __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
+    if (MM == kMatchLut) {
+        for (int k = threadIdx.x; k < 2048; k += 64) lut_s[k] = P.lutbits[k];
+        __syncthreads();
+    }
+    const uint32_t K = MM == kMatchSub ? P.sub_k : 1u;
+    if (MM == kMatchSub) {   // K <= kSubMaxSyms: at most 2048 words (the host pads the table to a whole word)
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(P.submat);
+        const int words = min((int)((K * K + 1) / 2), 2048);
+        for (int k = threadIdx.x; k < words; k += 64) lut_s[k] = src[k];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x, g = lane / L;
+    F f;
+    f.l = lane % L;
+    const uint32_t q = blockIdx.x * PPW + g;
+    const bool live = q < P.count;
+    uint32_t pair = 0;
+    const uint8_t* s1 = P.seq1;
+    const uint8_t* s2 = P.seq2;
+    f.m = 0;
+    f.n = 0;
+    BandGeom bg{0, 0, 0, 0x7ffffffe, -1};
+    if (live) {
+        pair = P.idx[q];
+        const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
+        f.m = (int32_t)(P.off1[pair + 1] - a1);
+        f.n = (int32_t)(P.off2[pair + 1] - a2);
+        s1 += a1;
+        s2 += a2;
+        bg = band_geom(f.m, f.n, (int32_t)P.band);
+    }
+    f.lo = bg.lo;
+    f.beff = bg.beff;
+    f.rlimE = (bg.beff - 2 * f.l * R + 1) >> 1;
+    f.rlimO = (bg.beff - 2 * f.l * R) >> 1;
+    f.gopen = P.gap_open;
+    f.ge = P.gap_extend;
+    f.goe = P.gap_open + P.gap_extend;
+    f.match = P.match;
+    f.mism = P.mismatch;
+    f.lut = lut_s;
+    f.sub = reinterpret_cast<const int16_t*>(lut_s);
+    f.best = (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
+    f.score = INT_MIN;
+    // steps without border cells and without cells outside the matrix: tA < t <= tB (idle lanes: all)
+    int32_t tA = INT_MIN, tB = INT_MAX;
+    if (live) {
+        tA = max(bg.hi, -bg.lo) - bg.lo;
+        tB = min(min(2 * f.m + bg.lo, 2 * f.n - bg.hi) - bg.lo, bg.tend - 1);   // (the last step takes M[m][n])
+    }
+    int32_t t0 = bg.tb, t1 = bg.tend;
+    for (int off = 32; off >= 1; off >>= 1) {
+        t0 = min(t0, __shfl_xor(t0, off));
+        t1 = max(t1, __shfl_xor(t1, off));
+        tA = max(tA, __shfl_xor(tA, off));
+        tB = min(tB, __shfl_xor(tB, off));
+    }
+    t0 = __builtin_amdgcn_readfirstlane(t0);
+    t1 = __builtin_amdgcn_readfirstlane(t1);
+    tA = __builtin_amdgcn_readfirstlane(tA);
+    tB = __builtin_amdgcn_readfirstlane(tB);
+
+    // (kMatchSub: a Seq1 symbol becomes its row base here, once, not in every cell that reads it)
+    auto sym1 = [&](int32_t x) -> uint32_t {
+        if (MM == kMatchSub) return (uint32_t)x < (uint32_t)f.m ? s1[x] * K : 0u;
+        return (uint32_t)x < (uint32_t)f.m ? s1[x] : 0u;
+    };
+    auto sym2 = [&](int32_t x) -> uint32_t { return (uint32_t)x < (uint32_t)f.n ? s2[x] : 0u; };
+    const int32_t h0 = t0 >> 1, h1 = t1 >> 1;
+    const int32_t ab = -f.l * R - 1, bb = f.l * R + f.lo - 1;   // A[r] = Seq1[h + ab - r], Bw[r] = Seq2[h + bb + r]
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        f.EM[r] = f.EX[r] = f.EY[r] = kBandNeg;
+        f.OM[r] = f.OX[r] = f.OY[r] = kBandNeg;
+        f.A[r] = sym1(h0 + ab - r);
+    }
+#pragma unroll
+    for (int r = 0; r <= R; ++r) f.Bw[r] = sym2(h0 + bb + r);
+
+    uint32_t* rec = REC && live ? P.rec + P.recoff[q] : nullptr;
+    uint32_t acc = 0;
+    auto store = [&](int32_t t) {
+        if (!REC) return;
+        const int32_t tp = t - bg.tb;
+        if (tp < 0 || t > bg.tend) return;
+        if (R <= 8) {
+            const int32_t s = tp % S;
+            acc |= f.w[0] << (s * 4 * R);
+            if (s == S - 1 || t == bg.tend) {
+                rec[(uint64_t)(tp / S) * L + f.l] = acc;
+                acc = 0;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < WPS; ++k) rec[((uint64_t)tp * WPS + k) * L + f.l] = f.w[k];
+        }
+    };
+
+    // symbols enter the windows PF iterations after their loads were issued (as sa_banded.hip)
+    constexpr int PF = 4;
+    uint32_t ca[PF], cb[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        ca[u] = sym1(h0 + u + 1 + ab);
+        cb[u] = sym2(h0 + u + 1 + bb + R);
+    }
+    for (int32_t hb = h0; hb <= h1; hb += PF) {
+        uint32_t na[PF], nb[PF];
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            na[u] = sym1(hb + PF + u + 1 + ab);
+            nb[u] = sym2(hb + PF + u + 1 + bb + R);
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int32_t h = hb + u, t = 2 * h;
+            if (h > h1) break;
+            if (t > tA && t + 1 <= tB) {
+                f.template step<0, false>(h);
+                store(t);
+                f.template step<1, false>(h);
+                store(t + 1);
+            } else {
+                f.template step<0, true>(h);
+                store(t);
+                f.template step<1, true>(h);
+                store(t + 1);
+            }
+#pragma unroll
+            for (int r = R - 1; r > 0; --r) f.A[r] = f.A[r - 1];
+            f.A[0] = ca[u];
+#pragma unroll
+            for (int r = 0; r < R; ++r) f.Bw[r] = f.Bw[r + 1];
+            f.Bw[R] = cb[u];
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            ca[u] = na[u];
+            cb[u] = nb[u];
+        }
+    }
+
+    // fold the pair's lanes
+    int32_t sc_i = 0, sc_j = 0, sc = f.score;
+    if (!LOCAL) {
+        for (int off = L / 2; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
+        sc_i = f.m;
+        sc_j = f.n;
+    } else {
+        long long b = f.best;
+        for (int off = L / 2; off >= 1; off >>= 1) {
+            const long long o = __shfl_xor(b, off);
+            b = o > b ? o : b;
+        }
+        sc = (int32_t)(b >> 32);
+        if (sc < 0) {   // no interior cell (an empty input): M[0][0], as the unbanded raw path
+            sc = 0;
+        } else {
+            const uint32_t pos = (uint32_t)b;
+            sc_i = (int32_t)(pos / (uint32_t)f.beff);
+            sc_j = sc_i + f.lo + (int32_t)(pos % (uint32_t)f.beff);
+        }
+    }
+    if (live && f.l == 0) {
+        sa_result* r = P.res + pair;
+        r->score = sc;
+        r->end_i = sc_i;
+        r->end_j = sc_j;
+        if (!REC) {
+            r->start_i = -1;
+            r->start_j = -1;
+            r->nops = 0;
+            r->flags = 0;
+            r->reserved = 0;
+        }
+    }
+}
+
+// The recording / record-free kernel of one (algorithm, R, L, match mode).
+template <bool LOCAL, int R, int L, int MM>
+hipError_t launch_band_affine_fill_rl(bool rec, const BandAffineParams& p, hipStream_t s) {
+    const uint32_t grid = (p.count + 64 / L - 1) / (64 / L);
+    if (rec) hipLaunchKernelGGL((banded_affine_fill_kernel<LOCAL, R, L, MM, true>), dim3(grid), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((banded_affine_fill_kernel<LOCAL, R, L, MM, false>), dim3(grid), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
+template <bool LOCAL, int MM>
+hipError_t launch_band_affine_fill_alg(int variant, bool rec, const BandAffineParams& p, hipStream_t s) {
+    static_assert(kBandAffineVariants == 7, "one case per variant of kBandR / kBandL below");
+    switch (variant) {
+        case 0: return launch_band_affine_fill_rl<LOCAL, 1, 16, MM>(rec, p, s);
+        case 1: return launch_band_affine_fill_rl<LOCAL, 2, 16, MM>(rec, p, s);
+        case 2: return launch_band_affine_fill_rl<LOCAL, 4, 16, MM>(rec, p, s);
+        case 3: return launch_band_affine_fill_rl<LOCAL, 4, 32, MM>(rec, p, s);
+        case 4: return launch_band_affine_fill_rl<LOCAL, 4, 64, MM>(rec, p, s);
+        case 5: return launch_band_affine_fill_rl<LOCAL, 8, 64, MM>(rec, p, s);
+        case 6: return launch_band_affine_fill_rl<LOCAL, 16, 64, MM>(rec, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+}  // namespace sa

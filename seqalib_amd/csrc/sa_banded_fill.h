@@ -1,0 +1,338 @@
+// sa_banded_fill.h — the banded Needleman-Wunsch / Smith-Waterman fill (sa_align_batch_banded,
+// sa_score_batch_banded, and the linear half of sa_align_batch_banded_matrix): an anti-diagonal sweep
+// over the in-band cells only, the whole band of a pair in the registers of one wave (or of 16 / 32
+// lanes of it), 2-bit direction records laid out by anti-diagonal.  DESIGN.md §2.11, §2.14.
+// Instantiated by sa_banded.hip (kMatchEq, kMatchLut) and sa_banded_sub.hip (kMatchSub), one
+// translation unit per match mode group, so that neither changes the other's code object.
+//
+// Geometry (BandGeom, sa_internal.h).  Cell (i, j) lies on diagonal k = j - i and anti-diagonal
+// d = i + j.  The band [lo, hi] is clipped to the matrix, lo' = max(lo, -m), hi' = min(hi, n) (the
+// cells cut off do not exist), c = k - lo' in [0, B') indexes its diagonals and t = d - lo' its
+// steps: step t holds the cells with c = t (mod 2), i = (t - c) / 2, j = i + lo' + c.  Lane l of the
+// pair's L lanes owns the 2R diagonals c = 2lR .. 2lR + 2R - 1; an even step computes its R even
+// ones (registers E[r], c = 2lR + 2r), an odd step its R odd ones (O[r], c = 2lR + 2r + 1):
+//   even step: left (i, j-1) = O[r-1] (r = 0: lane l-1's O[R-1], one DPP wave shift),
+//              up (i-1, j) = O[r], diagonal (i-1, j-1) = E[r] before the update;
+//   odd step:  left = E[r], up = E[r+1] (r = R-1: lane l+1's E[0], one DPP wave shift), diagonal O[r].
+// A cell that does not exist (outside the matrix, outside the band, c >= B') holds kBandNeg, so a
+// candidate read from it is below every real score (|score| < 2^29 is checked on the host) and is
+// neither the maximum nor equal to it.  With h = t / 2 the lane's cells of both steps are in rows
+// h - lR - r, so it keeps R Seq1 symbols and R + 1 Seq2 symbols in registers and slides both windows
+// by one symbol per h.
+//
+// Match modes (MM).  kMatchEq: byte equality.  kMatchLut: the 256 x 256 bit table, 8 KiB of LDS.
+// kMatchSub (the matrix calls): the sequences hold symbol codes 0..K-1 and the diagonal term is
+// S[code(a)][code(b)], read from the dense K x K int16 table that takes the bit table's LDS slot;
+// A[r] holds the row base code(a) * K, multiplied once when the symbol is loaded, Bw[] plain codes,
+// so the cell's term is one add and one 16-bit LDS read, and match / mism are not read.  A window
+// position outside its sequence holds 0 in every mode: entry 0 of the table (the host never passes
+// an empty one).
+#pragma once
+#include "sa_internal.h"
+
+namespace sa {
+namespace {
+
+__device__ __forceinline__ int32_t from_lower_lane(int32_t v) {   // lane l takes lane l - 1's, lane 0 kBandNeg
+    return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ int32_t from_upper_lane(int32_t v) {   // lane l takes lane l + 1's, lane 63 kBandNeg
+    return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x130, 0xf, 0xf, false);
+}
+
+template <int ALG, int R, int L, int MM, bool REC>
+struct BandFill {
+    static constexpr int S = R <= 16 ? 16 / R : 1;   // steps per record word
+    int32_t E[R], O[R];
+    uint32_t A[R], Bw[R + 1];
+    int32_t m, n, lo, beff, rlimE, rlimO, l;
+    int32_t G, match, mism;
+    const uint32_t* lut;
+    const int16_t* sub;  // kMatchSub: the K x K table in LDS
+    long long best;      // SW: (h << 32 | i * beff + c) of the last row-major maximum
+    int32_t score;       // NW: H[m][n]
+    uint32_t w0, w1;     // the step's 2-bit codes (w1: cells 16..31 of R = 32)
+
+    // One step.  PAR: 0 even (E), 1 odd (O).  EDGE: the step may hold border cells or cells outside
+    // the matrix; otherwise every cell with c < B' is an interior cell.
+    template <int PAR, bool EDGE>
+    __device__ __forceinline__ void step(int32_t h) {
+        int32_t sh;
+        if (PAR == 0) {
+            sh = from_lower_lane(O[R - 1]);
+            if (l == 0) sh = kBandNeg;
+        } else {
+            sh = from_upper_lane(E[0]);
+            if (l == L - 1) sh = kBandNeg;
+        }
+        const int32_t i0 = h - l * R, j0 = h + l * R + lo + PAR;
+        const int32_t rlim = PAR ? rlimO : rlimE;
+        uint32_t pos = (uint32_t)i0 * (uint32_t)beff + (uint32_t)(2 * l * R + PAR);
+        const uint32_t dpos = 2u - (uint32_t)beff;
+        w0 = 0;
+        w1 = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int32_t left, up, dg;
+            uint32_t a = A[r], b;
+            if (PAR == 0) {
+                left = r ? O[r > 0 ? r - 1 : 0] : sh;
+                up = O[r];
+                dg = E[r];
+                b = Bw[r];
+            } else {
+                left = E[r];
+                up = r < R - 1 ? E[r < R - 1 ? r + 1 : r] : sh;
+                dg = O[r];
+                b = Bw[r + 1];
+            }
+            int32_t cd;
+            if (MM == kMatchSub) {
+                cd = dg + sub[a + b];
+            } else {
+                bool mt;
+                if (MM == kMatchLut) mt = (lut[(a << 3) | (b >> 5)] >> (b & 31)) & 1u;
+                else mt = a == b;
+                cd = dg + (mt ? match : mism);
+            }
+            const int32_t cu = up + G, cl = left + G;
+            int32_t hv = max(max(cd, cu), cl);
+            if (ALG == SA_SW) hv = max(hv, 0);
+            uint32_t code = hv == cd ? 1u : hv == cu ? 2u : 3u;
+            if (ALG == SA_SW && hv == 0) code = 0;
+            const int32_t i = i0 - r, j = j0 + r;
+            const bool inb = r < rlim;
+            bool interior = inb;
+            int32_t val;
+            if (EDGE) {
+                interior = inb && (uint32_t)(i - 1) < (uint32_t)m && (uint32_t)(j - 1) < (uint32_t)n;
+                const bool border = inb && ((i == 0 && (uint32_t)j <= (uint32_t)n) || (j == 0 && (uint32_t)i <= (uint32_t)m));
+                const int32_t bval = ALG == SA_NW ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)G) : 0;
+                val = interior ? hv : border ? bval : kBandNeg;
+                if (ALG == SA_NW && inb && i == m && j == n) score = val;
+            } else {
+                val = inb ? hv : kBandNeg;
+            }
+            if (ALG == SA_SW) {
+                const long long key = (long long)(((unsigned long long)(uint32_t)hv << 32) | pos);
+                if (interior && key > best) best = key;
+                pos += dpos;
+            }
+            if (PAR == 0) E[r] = val;
+            else O[r] = val;
+            if (REC) {
+                if (r < 16) w0 |= code << (2 * (r & 15));
+                else w1 |= code << (2 * (r & 15));
+            }
+        }
+    }
+};
+
+template <int ALG, int R, int L, int MM, bool REC>
+__global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
+    using F = BandFill<ALG, R, L, MM, REC>;
+    constexpr int PPW = 64 / L, S = F::S;
+    __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
+    if (MM == kMatchLut) {
+        for (int k = threadIdx.x; k < 2048; k += 64) lut_s[k] = P.lutbits[k];
+        __syncthreads();
+    }
+    const uint32_t K = MM == kMatchSub ? P.sub_k : 1u;
+    if (MM == kMatchSub) {   // K <= kSubMaxSyms: at most 2048 words (the host pads the table to a whole word)
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(P.submat);
+        const int words = min((int)((K * K + 1) / 2), 2048);
+        for (int k = threadIdx.x; k < words; k += 64) lut_s[k] = src[k];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x, g = lane / L;
+    F f;
+    f.l = lane % L;
+    const uint32_t q = blockIdx.x * PPW + g;
+    const bool live = q < P.count;
+    uint32_t pair = 0;
+    const uint8_t* s1 = P.seq1;
+    const uint8_t* s2 = P.seq2;
+    f.m = 0;
+    f.n = 0;
+    BandGeom bg{0, 0, 0, 0x7ffffffe, -1};
+    if (live) {
+        pair = P.idx[q];
+        const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
+        f.m = (int32_t)(P.off1[pair + 1] - a1);
+        f.n = (int32_t)(P.off2[pair + 1] - a2);
+        s1 += a1;
+        s2 += a2;
+        bg = band_geom(f.m, f.n, (int32_t)P.band);
+    }
+    f.lo = bg.lo;
+    f.beff = bg.beff;
+    f.rlimE = (bg.beff - 2 * f.l * R + 1) >> 1;
+    f.rlimO = (bg.beff - 2 * f.l * R) >> 1;
+    f.G = P.gap;
+    f.match = P.match;
+    f.mism = P.mismatch;
+    f.lut = lut_s;
+    f.sub = reinterpret_cast<const int16_t*>(lut_s);
+    f.best = (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
+    f.score = INT_MIN;
+    // steps without border cells and without cells outside the matrix: tA < t <= tB (idle lanes: all)
+    int32_t tA = INT_MIN, tB = INT_MAX;
+    if (live) {
+        tA = max(bg.hi, -bg.lo) - bg.lo;
+        tB = min(min(2 * f.m + bg.lo, 2 * f.n - bg.hi) - bg.lo, bg.tend - 1);   // (the last step takes H[m][n])
+    }
+    int32_t t0 = bg.tb, t1 = bg.tend;
+    for (int off = 32; off >= 1; off >>= 1) {
+        t0 = min(t0, __shfl_xor(t0, off));
+        t1 = max(t1, __shfl_xor(t1, off));
+        tA = max(tA, __shfl_xor(tA, off));
+        tB = min(tB, __shfl_xor(tB, off));
+    }
+    t0 = __builtin_amdgcn_readfirstlane(t0);
+    t1 = __builtin_amdgcn_readfirstlane(t1);
+    tA = __builtin_amdgcn_readfirstlane(tA);
+    tB = __builtin_amdgcn_readfirstlane(tB);
+
+    // (kMatchSub: a Seq1 symbol becomes its row base here, once, not in every cell that reads it)
+    auto sym1 = [&](int32_t x) -> uint32_t {
+        if (MM == kMatchSub) return (uint32_t)x < (uint32_t)f.m ? s1[x] * K : 0u;
+        return (uint32_t)x < (uint32_t)f.m ? s1[x] : 0u;
+    };
+    auto sym2 = [&](int32_t x) -> uint32_t { return (uint32_t)x < (uint32_t)f.n ? s2[x] : 0u; };
+    const int32_t h0 = t0 >> 1, h1 = t1 >> 1;
+    const int32_t ab = -f.l * R - 1, bb = f.l * R + f.lo - 1;   // A[r] = Seq1[h + ab - r], Bw[r] = Seq2[h + bb + r]
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        f.E[r] = kBandNeg;
+        f.O[r] = kBandNeg;
+        f.A[r] = sym1(h0 + ab - r);
+    }
+#pragma unroll
+    for (int r = 0; r <= R; ++r) f.Bw[r] = sym2(h0 + bb + r);
+
+    uint32_t* rec = REC && live ? P.rec + P.recoff[q] : nullptr;
+    uint32_t acc = 0;
+    auto store = [&](int32_t t) {
+        if (!REC) return;
+        const int32_t tp = t - bg.tb;
+        if (tp < 0 || t > bg.tend) return;
+        if (R <= 16) {
+            const int32_t s = tp % S;
+            acc |= f.w0 << (s * 2 * R);
+            if (s == S - 1 || t == bg.tend) {
+                rec[(uint64_t)(tp / S) * L + f.l] = acc;
+                acc = 0;
+            }
+        } else {
+            rec[(uint64_t)tp * 2 * L + f.l] = f.w0;
+            rec[((uint64_t)tp * 2 + 1) * L + f.l] = f.w1;
+        }
+    };
+
+    // The symbols that enter the windows after iteration h are loaded PF iterations ahead,
+    // a block at a time, so that no step waits for a load issued in its own iteration.
+    constexpr int PF = 4;
+    uint32_t ca[PF], cb[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        ca[u] = sym1(h0 + u + 1 + ab);
+        cb[u] = sym2(h0 + u + 1 + bb + R);
+    }
+    for (int32_t hb = h0; hb <= h1; hb += PF) {
+        uint32_t na[PF], nb[PF];
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            na[u] = sym1(hb + PF + u + 1 + ab);
+            nb[u] = sym2(hb + PF + u + 1 + bb + R);
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int32_t h = hb + u, t = 2 * h;
+            if (h > h1) break;
+            if (t > tA && t + 1 <= tB) {
+                f.template step<0, false>(h);
+                store(t);
+                f.template step<1, false>(h);
+                store(t + 1);
+            } else {
+                f.template step<0, true>(h);
+                store(t);
+                f.template step<1, true>(h);
+                store(t + 1);
+            }
+#pragma unroll
+            for (int r = R - 1; r > 0; --r) f.A[r] = f.A[r - 1];
+            f.A[0] = ca[u];
+#pragma unroll
+            for (int r = 0; r < R; ++r) f.Bw[r] = f.Bw[r + 1];
+            f.Bw[R] = cb[u];
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            ca[u] = na[u];
+            cb[u] = nb[u];
+        }
+    }
+
+    // fold the pair's lanes
+    int32_t sc_i = 0, sc_j = 0, sc = f.score;
+    if (ALG == SA_NW) {
+        for (int off = L / 2; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
+        sc_i = f.m;
+        sc_j = f.n;
+    } else {
+        long long b = f.best;
+        for (int off = L / 2; off >= 1; off >>= 1) {
+            const long long o = __shfl_xor(b, off);
+            b = o > b ? o : b;
+        }
+        sc = (int32_t)(b >> 32);
+        if (sc < 0) {   // no interior cell: an empty input
+            sc = INT_MIN;
+        } else {
+            const uint32_t pos = (uint32_t)b;
+            sc_i = (int32_t)(pos / (uint32_t)f.beff);
+            sc_j = sc_i + f.lo + (int32_t)(pos % (uint32_t)f.beff);
+        }
+    }
+    if (live && f.l == 0) {
+        sa_result* r = P.res + pair;
+        r->score = sc;
+        r->end_i = sc_i;
+        r->end_j = sc_j;
+        if (!REC) {
+            r->start_i = -1;
+            r->start_j = -1;
+            r->nops = 0;
+            r->flags = 0;
+            r->reserved = 0;
+        }
+    }
+}
+
+// The recording / record-free kernel of one (algorithm, R, L, match mode).
+template <int ALG, int R, int L, int MM>
+hipError_t launch_band_fill_rl(bool rec, const BandParams& p, hipStream_t s) {
+    const uint32_t grid = (p.count + 64 / L - 1) / (64 / L);
+    if (rec) hipLaunchKernelGGL((banded_fill_kernel<ALG, R, L, MM, true>), dim3(grid), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((banded_fill_kernel<ALG, R, L, MM, false>), dim3(grid), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
+template <int ALG, int MM>
+hipError_t launch_band_fill_alg(int variant, bool rec, const BandParams& p, hipStream_t s) {
+    switch (variant) {
+        case 0: return launch_band_fill_rl<ALG, 1, 16, MM>(rec, p, s);
+        case 1: return launch_band_fill_rl<ALG, 2, 16, MM>(rec, p, s);
+        case 2: return launch_band_fill_rl<ALG, 4, 16, MM>(rec, p, s);
+        case 3: return launch_band_fill_rl<ALG, 4, 32, MM>(rec, p, s);
+        case 4: return launch_band_fill_rl<ALG, 4, 64, MM>(rec, p, s);
+        case 5: return launch_band_fill_rl<ALG, 8, 64, MM>(rec, p, s);
+        case 6: return launch_band_fill_rl<ALG, 16, 64, MM>(rec, p, s);
+        case 7: return launch_band_fill_rl<ALG, 32, 64, MM>(rec, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+}  // namespace sa

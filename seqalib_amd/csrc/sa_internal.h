@@ -444,8 +444,16 @@ struct BandParams {
     int32_t gap, match, mismatch;   // mismatch: kBandNeg when mismatches are not allowed
     int allow;
     int R, L;                  // the variant that wrote rec (the walk)
+    // kMatchSub (the matrix band calls): seq1 / seq2 hold symbol codes 0..sub_k-1, submat is the dense
+    // sub_k x sub_k int16 table over them (row stride sub_k, padded to a whole 32-bit word, sub_k >= 1),
+    // lutbits the label table over codes (the walk), match / mismatch are not read, allow = 1
+    const int16_t* submat;
+    uint32_t sub_k;
 };
-hipError_t launch_banded_fill(int algo, int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
+// mm: kMatchEq, kMatchLut (lutbits) or kMatchSub (submat; instantiated in sa_banded_sub.hip /
+// sa_banded_affine_sub.hip, reached through these launchers)
+hipError_t launch_banded_fill(int algo, int variant, int mm, bool rec, const BandParams& p, hipStream_t s);
+hipError_t launch_banded_fill_sub(int algo, int variant, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_tb(int algo, bool lut, const BandParams& p, hipStream_t s);
 
 // The banded affine path (sa_banded_affine.hip; sa_align_batch_banded_affine /
@@ -467,6 +475,7 @@ inline uint64_t band_affine_rec_words(const BandGeom& g, int v) {
 struct BandAffineParams : BandParams {   // (gap is unused)
     int32_t gap_open, gap_extend;
 };
-hipError_t launch_banded_affine_fill(int algo, int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_fill(int algo, int variant, int mm, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_fill_sub(int algo, int variant, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_tb(int algo, bool lut, const BandAffineParams& p, hipStream_t s);
 }  // namespace sa

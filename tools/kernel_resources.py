@@ -19,8 +19,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-devic
          "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
 NAME = re.compile(r"Function Name: _ZN2sa11fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
 FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
-BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E")
-AFFINE = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E")
+BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d)ELb(\d)E")
+AFFINE = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb(\d)ELi(\d+)ELi(\d+)ELi(\d)ELb(\d)E")
 SO2 = re.compile(r"Function Name: _ZN2sa15fill_so2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
 CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
@@ -43,12 +43,12 @@ def parse(text):
             rows.append(cur)
             continue
         m = BANDED.search(line)
-        if m:   # the banded fills (sa_banded.hip): algorithm, R, L, LUT, REC
+        if m:   # the banded fills (sa_banded.hip): algorithm, R, L, match mode, REC
             cur = {"banded": tuple(int(x) for x in m.groups())}
             rows.append(cur)
             continue
         m = AFFINE.search(line)
-        if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, LUT, REC
+        if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
             cur = {"banded": (3 - g[0],) + g[1:]}
             rows.append(cur)
