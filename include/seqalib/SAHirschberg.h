@@ -40,6 +40,33 @@ public:
         return out;
     }
 
+    // Extension: ends-free (semi-global) banded NW (Hirschberg's scores are NW's; the result is an NW alignment) (sa_align_batch_banded_ends_free /
+    // sa_score_batch_banded_ends_free): as the banded forms, but the heads / tails of the sequences that
+    // freeEnds names (an OR of SA_FREE_SEQ1_BEGIN, SA_FREE_SEQ1_END, SA_FREE_SEQ2_BEGIN, SA_FREE_SEQ2_END)
+    // stay unaligned at no cost -- a read in a window: SEQ2_BEGIN | SEQ2_END with the read as Seq1; two
+    // overlapping reads: SEQ1_BEGIN | SEQ2_END.  The aligned core is padded to both whole sequences the
+    // way forceGlobal pads a local alignment; getScore() is the core's score.
+    // (std::runtime_error where it applies).
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band, unsigned freeEnds) {
+        std::vector<sa_result> res;
+        auto out = seqalib::detail::run<SA_HIRSCHBERG, HirschbergSA, ContainerType, Ty, Blank>(*this, pairs, res, seqalib::detail::band_of(band),
+                                                                                (long long)freeEnds);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band,
+                                           unsigned freeEnds) {
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_HIRSCHBERG, HirschbergSA, ContainerType, Ty>(*this, pairs, res, seqalib::detail::band_of(band),
+                                                                       (long long)freeEnds);
+        std::vector<ScoreSystemType> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.push_back(r.score);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+
     // Extension: NW score H[m][n] of the last alignment (the reference exposes none).
     ScoreSystemType getScore() const { return LastScore; }
 };

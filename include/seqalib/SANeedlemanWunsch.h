@@ -50,20 +50,37 @@ public:
         return scoreBatch(pairs, seqalib::detail::band_of(band));
     }
 
+    // Extension: ends-free (semi-global) banded NW (sa_align_batch_banded_ends_free /
+    // sa_score_batch_banded_ends_free): as the banded forms, but the heads / tails of the sequences that
+    // freeEnds names (an OR of SA_FREE_SEQ1_BEGIN, SA_FREE_SEQ1_END, SA_FREE_SEQ2_BEGIN, SA_FREE_SEQ2_END)
+    // stay unaligned at no cost -- a read in a window: SEQ2_BEGIN | SEQ2_END with the read as Seq1; two
+    // overlapping reads: SEQ1_BEGIN | SEQ2_END.  The aligned core is padded to both whole sequences the
+    // way forceGlobal pads a local alignment; getScore() is the core's score.  Not combinable with
+    // setSubstitution() (std::runtime_error).
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band, unsigned freeEnds) {
+        return alignBatch(pairs, seqalib::detail::band_of(band), (long long)freeEnds);
+    }
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band,
+                                           unsigned freeEnds) {
+        return scoreBatch(pairs, seqalib::detail::band_of(band), (long long)freeEnds);
+    }
+
     // Extension: H[m][n] of the last alignment.
     ScoreSystemType getScore() const { return LastScore; }
 
 private:
     std::vector<AlignedSequence<Ty, Blank>> alignBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                                                       long long band) {
+                                                       long long band, long long free_ends = seqalib::detail::kNoFreeEnds) {
         std::vector<sa_result> res;
-        auto out = seqalib::detail::run<SA_NW, NeedlemanWunschSA, ContainerType, Ty, Blank>(*this, pairs, res, band);
+        auto out = seqalib::detail::run<SA_NW, NeedlemanWunschSA, ContainerType, Ty, Blank>(*this, pairs, res, band, free_ends);
         if (!res.empty()) LastScore = res.back().score;
         return out;
     }
-    std::vector<ScoreSystemType> scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, long long band) {
+    std::vector<ScoreSystemType> scoreBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, long long band,
+                                            long long free_ends = seqalib::detail::kNoFreeEnds) {
         std::vector<sa_result> res;
-        seqalib::detail::run_scores<SA_NW, NeedlemanWunschSA, ContainerType, Ty>(*this, pairs, res, band);
+        seqalib::detail::run_scores<SA_NW, NeedlemanWunschSA, ContainerType, Ty>(*this, pairs, res, band, free_ends);
         std::vector<ScoreSystemType> out;
         out.reserve(res.size());
         for (auto& r : res) out.push_back(r.score);

@@ -192,7 +192,8 @@ constexpr size_t kChunkPairs = SIZE_MAX;
 // callbacks hand each landed range to a builder thread (which fans out over the host threads).
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty, Ty Blank>
 std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                                            std::vector<sa_result>& res, long long band = kNoBand) {
+                                            std::vector<sa_result>& res, long long band = kNoBand,
+                                            long long free_ends = kNoFreeEnds) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
@@ -207,7 +208,8 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
             // (align() throws for it once the GPU call returns)
             if (r.flags & (SA_FLAG_DIVERGED | SA_FLAG_TIMEOUT)) continue;
             build_from_ops<Ty, Blank>(*pairs[p].first, *pairs[p].second, r, ops.data() + off[p], out[p]);
-            const bool local = (ALGO == SA_SW || ALGO == SA_LOCAL_GOTOH) && !(r.flags & SA_FLAG_SIZE_HACK);
+            // (an ends-free alignment is padded like a local one: its free ends against Blanks)
+            const bool local = ((ALGO == SA_SW || ALGO == SA_LOCAL_GOTOH) && !(r.flags & SA_FLAG_SIZE_HACK)) || free_ends != kNoFreeEnds;
             if (local)
                 self.forceGlobal(*pairs[p].first, *pairs[p].second, out[p], r.start_i, r.start_j, r.end_i, r.end_j);
         }
@@ -222,7 +224,7 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
     // (a banded call is one range, and so is a matrix call)
     const size_t G = band == kNoBand && !sub && cp <= P / 2 ? (P + cp - 1) / cp : 1;
     if (G == 1) {
-        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub);
+        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub, free_ends);
         build_range(0, P);
         tm.lap("AlignedSequence lists");
         return out;
@@ -284,13 +286,13 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
 // buffers) over the batch; res[p] holds pair p's score and end cell.
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty>
 void run_scores(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                std::vector<sa_result>& res, long long band = kNoBand) {
+                std::vector<sa_result>& res, long long band = kNoBand, long long free_ends = kNoFreeEnds) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
     res.clear();
     const std::function<ScoreSystemType(Ty, Ty)>* sub = self.getSubstitution() ? &self.getSubstitution() : nullptr;
-    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub);
+    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub, free_ends);
 }
 
 }  // namespace detail

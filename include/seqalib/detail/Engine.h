@@ -397,6 +397,15 @@ inline long long band_of(size_t band) {
     if (band > 0xffffffffull) throw std::runtime_error("seqalib: band does not fit 32 bits");
     return (long long)band;
 }
+// free_ends >= 0: the ends-free banded call (sa_align_batch_banded_ends_free / sa_score_batch_banded_ends_free)
+// with these SA_FREE_* bits; it needs a band and takes match / mismatch scorings only.
+constexpr long long kNoFreeEnds = -1;
+inline uint32_t free_ends_arg(long long free_ends, long long band, bool sub) {
+    if (band == kNoBand) throw std::runtime_error("seqalib: free ends need a band");
+    if (sub) throw std::runtime_error("seqalib: substitution scoring and free ends cannot be combined");
+    if (free_ends > 0xffffffffLL) throw std::runtime_error("seqalib: freeEnds does not fit 32 bits");
+    return (uint32_t)free_ends;
+}
 inline void banded_needs_table(bool overflow) {
     if (overflow)
         throw std::runtime_error("seqalib: banded calls take batches of at most " + std::to_string(kBandedMaxSymbols) +
@@ -436,7 +445,9 @@ template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubF
 void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
            std::vector<sa_result>& res, raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off,
-           uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand, const SubFnTy* sub = nullptr) {
+           uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand, const SubFnTy* sub = nullptr,
+           long long free_ends = kNoFreeEnds) {
+    const uint32_t fe = free_ends == kNoFreeEnds ? 0 : free_ends_arg(free_ends, band, sub != nullptr);
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -487,7 +498,12 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     ops_off.resize(n);
     for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
     tm.lap("match table + buffers");
-    if (band != kNoBand) {
+    if (free_ends != kNoFreeEnds) {
+        check(sa_align_batch_banded_ends_free(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                              has_fn ? lut.data() : nullptr, band_arg(band), fe, res.data(), ops.data(), cap),
+              "sa_align_batch_banded_ends_free");
+        if (on_chunk && n) on_chunk(0, n);
+    } else if (band != kNoBand) {
         const bool aff = banded_is_affine(algo);
         check((aff ? sa_align_batch_banded_affine : sa_align_batch_banded)(
                   context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, has_fn ? lut.data() : nullptr,
@@ -523,7 +539,8 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
 template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubFnTy = std::function<int(Ty, Ty)>>
 void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
-           long long band = kNoBand, const SubFnTy* sub = nullptr) {
+           long long band = kNoBand, const SubFnTy* sub = nullptr, long long free_ends = kNoFreeEnds) {
+    const uint32_t fe = free_ends == kNoFreeEnds ? 0 : free_ends_arg(free_ends, band, sub != nullptr);
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -553,6 +570,11 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
         std::vector<uint8_t> lut;
         if (has_fn) lut = build_lut(coder, fn);
         const bool aff = banded_is_affine(algo);
+        if (free_ends != kNoFreeEnds)
+            check(sa_score_batch_banded_ends_free(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                                  has_fn ? lut.data() : nullptr, band_arg(band), fe, res.data()),
+                  "sa_score_batch_banded_ends_free");
+        else
         check((aff ? sa_score_batch_banded_affine : sa_score_batch_banded)(
                   context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n, has_fn ? lut.data() : nullptr,
                   band_arg(band), res.data()),

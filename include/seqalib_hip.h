@@ -431,6 +431,65 @@ int sa_score_batch_banded_matrix(sa_ctx* ctx, int algo, const sa_scoring* scorin
                                  const int16_t* submat, const uint8_t* match_lut, uint32_t band,
                                  sa_result* results);
 
+/* Ends-free (semi-global) banded alignment: banded NW / banded GlobalGotoh in which the unaligned head
+ * or tail of a sequence may cost nothing -- a read inside a reference window (fit: SA_FREE_SEQ2_BEGIN |
+ * SA_FREE_SEQ2_END with the read as Seq1), two overlapping reads (overlap: SA_FREE_SEQ1_BEGIN |
+ * SA_FREE_SEQ2_END, a suffix of Seq1 against a prefix of Seq2, or the mirrored pair of flags), a primer
+ * against a read end (prefix / suffix: one END or one BEGIN flag). */
+#define SA_FREE_SEQ1_BEGIN 1   /* leading Seq1 symbols may stay unaligned at no cost  */
+#define SA_FREE_SEQ1_END   2   /* trailing Seq1 symbols may stay unaligned at no cost */
+#define SA_FREE_SEQ2_BEGIN 4   /* leading Seq2 symbols ...                            */
+#define SA_FREE_SEQ2_END   8   /* trailing Seq2 symbols ...                           */
+/* Band, recurrence, the rule that a term which would read a cell outside the band is no candidate, tie
+ * order, records, traceback order and op codes are those of sa_align_batch_banded with SA_NW
+ * (algo SA_NW, or SA_HIRSCHBERG meaning NW: 2-bit records, up to 4096 band diagonals inside the matrix)
+ * or of sa_align_batch_banded_affine with SA_GLOBAL_GOTOH (4-bit records, up to 2048), with exactly
+ * these changes, free_ends being any OR of the four flags:
+ * Borders.  With SA_FREE_SEQ1_BEGIN the in-band cells (i, 0) hold H = 0 (GlobalGotoh: M = 0); without it
+ *   i * gap (gap_open + i * gap_extend).  SA_FREE_SEQ2_BEGIN does the same for (0, j).  (0, 0) is 0.
+ *   GlobalGotoh's X = Y = -10000 on every border cell, as in the affine call.
+ * End cell.  The candidates are these in-band cells, border cells included: (m, n); with
+ *   SA_FREE_SEQ1_END every (i, n); with SA_FREE_SEQ2_END every (m, j).  The end cell is the last
+ *   candidate in row-major order that holds the maximum of H (M) over the candidates, so (m, n) wins
+ *   ties; score is that value, (end_i, end_j) that cell.  A negative score is a score like any other.
+ * Walk.  From the end cell (GlobalGotoh: in type 0), with the banded call's candidate order / state
+ *   machine; the symbols after the end cell produce no op.  At j == 0: stop with SA_FREE_SEQ1_BEGIN, else
+ *   'U' down to (0, 0).  At i == 0: stop with SA_FREE_SEQ2_BEGIN, else 'L'.  (start_i, start_j) is where
+ *   the walk stopped; flags = 0.
+ * free_ends == 0: every result field and every op equals sa_align_batch_banded's (SA_NW) /
+ *   sa_align_batch_banded_affine's (SA_GLOBAL_GOTOH).
+ * Score call: start = (-1, -1), nops = 0, reserved = 0, flags = 0; no records, no walk,
+ *   traceback_ms == 0; score and end cell as the align call's.
+ * The band is unchanged: lo = min(0, n - m) - w, hi = max(0, n - m) + w.  It holds every start diagonal
+ *   a Seq1 of length m can have inside a Seq2 of length n (and the reverse) plus w of slack, so w bounds
+ *   how far outside the corner-to-corner corridor a free start or end may lie: an overlap of two
+ *   equal-length reads can leave at most w symbols of each free.
+ * Status codes (all these checks are made before the context is looked at, so they give the same status
+ * with a NULL context; a NULL context with valid arguments: SA_ERR_ARG):
+ *   algo: SA_SW, SA_LOCAL_GOTOH, SA_MYERS_MILLER: SA_ERR_UNSUPPORTED; an invalid value: SA_ERR_ARG.
+ *   free_ends > 15: SA_ERR_ARG.
+ *   Every other argument check, pair limit and status code of sa_align_batch_banded with SA_NW /
+ *   sa_align_batch_banded_affine with SA_GLOBAL_GOTOH, unchanged: band >= 2^31 SA_ERR_ARG;
+ *   allow_mismatch == 0 with band == 0, gap_extend > 0 (GlobalGotoh), the 2^29 score bounds, a sequence
+ *   of >= 2^24 symbols, more than 4096 / 2048 band diagonals inside the matrix: SA_ERR_UNSUPPORTED.
+ *   There is no (m + 1) * diagonals < 2^31 limit: the end-cell search orders its at most m + n + 1
+ *   candidates by position along the last column and then the last row.
+ * Records, workspace, launch splitting under sa_set_workspace_limit and the joining of neighbouring
+ * variants are the banded calls'.  There is no plan query of its own: sa_banded_plan_query (SA_NW) /
+ * sa_banded_affine_plan_query (SA_GLOBAL_GOTOH) describe these calls too.  sa_last_timings works after
+ * either call; sa_last_plan_ex reports SA_KERNEL_BANDED, the cells per lane and step of the widest
+ * variant the call used, 1 wave, and SA_RECORDS_BAND2 / SA_RECORDS_BAND4 / SA_RECORDS_NONE. */
+int sa_align_batch_banded_ends_free(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                    const uint8_t* seq1, const uint64_t* seq1_off,
+                                    const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                    const uint8_t* match_lut, uint32_t band, uint32_t free_ends,
+                                    sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_banded_ends_free(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                    const uint8_t* seq1, const uint64_t* seq1_off,
+                                    const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                    const uint8_t* match_lut, uint32_t band, uint32_t free_ends,
+                                    sa_result* results);
+
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events
  * recorded on the stream they ran on: total fill-kernel ms, total traceback-kernel ms, and the
  * number of fill launches.  Waits for those events. */

@@ -47,6 +47,8 @@ SA_RECORDS_FLAGS, SA_RECORDS_TAGS, SA_RECORDS_SCORE_ONLY = 0, 1, 2
 SA_RECORDS_NONE = 3   # score calls on the int32 / small-call kernels: nothing stored for a traceback
 SA_RECORDS_BAND2 = 4  # banded align calls: 2 bits per in-band cell, laid out by anti-diagonal
 SA_RECORDS_BAND4 = 5  # banded affine align calls: 4 bits per in-band cell
+# free_ends of the ends-free banded calls (sa_align_batch_banded_ends_free): which unaligned heads / tails cost nothing
+SA_FREE_SEQ1_BEGIN, SA_FREE_SEQ1_END, SA_FREE_SEQ2_BEGIN, SA_FREE_SEQ2_END = 1, 2, 4, 8
 SA_HOOK_HAND_TAG, SA_HOOK_POISON_WS, SA_HOOK_F16 = 1, 2, 3   # sa_test_hook (tests only)
 INT32_MIN = -(2 ** 31)
 
@@ -157,6 +159,10 @@ def load_library():
                                                C.c_uint32, vp, vp, C.c_uint64]
     L.sa_score_batch_banded_matrix.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
                                                C.c_uint32, vp]
+    L.sa_align_batch_banded_ends_free.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
+                                                  C.c_uint32, C.c_uint32, vp, vp, C.c_uint64]
+    L.sa_score_batch_banded_ends_free.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
+                                                  C.c_uint32, C.c_uint32, vp]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
     L.sa_last_kernel_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sa_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p, u64p]
@@ -178,6 +184,7 @@ def load_library():
                "sa_align_batch_banded_affine", "sa_score_batch_banded_affine", "sa_banded_affine_plan_query",
                "sa_align_batch_matrix", "sa_score_batch_matrix", "sa_matrix_plan_query",
                "sa_align_batch_banded_matrix", "sa_score_batch_banded_matrix",
+               "sa_align_batch_banded_ends_free", "sa_score_batch_banded_ends_free",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -333,6 +340,13 @@ def _band_arg(band) -> int:
     if band < 0 or band > 0xFFFFFFFF:
         raise SeqalibError(f"band must be in [0, 2^32): {band}")
     return band
+
+
+def _free_ends_arg(free_ends) -> int:
+    free_ends = int(free_ends)
+    if free_ends < 0 or free_ends > 0xFFFFFFFF:
+        raise SeqalibError(f"free_ends must be an OR of SA_FREE_*: {free_ends}")
+    return free_ends
 
 
 def _as_bytes(s) -> bytes:
@@ -533,7 +547,36 @@ class Engine:
         Returns (results, ops) as align_packed."""
         return self._align_banded_call("sa_align_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
 
-    def _align_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut):
+    def align_banded_ends_free_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                      s2: np.ndarray, off2: np.ndarray, band: int, free_ends: int,
+                                      lut: Optional[np.ndarray] = None):
+        """Ends-free banded host-buffer batch (sa_align_batch_banded_ends_free): banded NW (SA_NW,
+        SA_HIRSCHBERG) or banded GlobalGotoh in which the heads / tails named by `free_ends` (an OR of
+        SA_FREE_*) stay unaligned at no cost.  Returns (results, ops) as align_packed."""
+        return self._align_banded_call("sa_align_batch_banded_ends_free", algo, scoring, s1, off1, s2, off2, band, lut,
+                                       (_free_ends_arg(free_ends),))
+
+    def score_banded_ends_free_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                      s2: np.ndarray, off2: np.ndarray, band: int, free_ends: int,
+                                      lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Ends-free banded score batch (sa_score_batch_banded_ends_free): the results array (start = -1, nops = 0)."""
+        return self._score_banded_call("sa_score_batch_banded_ends_free", algo, scoring, s1, off1, s2, off2, band, lut,
+                                       (_free_ends_arg(free_ends),))
+
+    def align_banded_ends_free(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                               free_ends: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the ends-free banded call."""
+        def call(algo, scoring, s1, off1, s2, off2, band, lut):
+            return self.align_banded_ends_free_packed(algo, scoring, s1, off1, s2, off2, band, free_ends, lut)
+        return self._align_banded_pairs(call, algo, scoring, pairs, band, lut)
+
+    def score_banded_ends_free(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                               free_ends: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the ends-free banded call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_banded_ends_free_packed(algo, scoring, s1, off1, s2, off2, band, free_ends, lut))
+
+    def _align_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=()):
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
@@ -548,7 +591,7 @@ class Engine:
             lut_p = _ptr(lut)
         sc = scoring._c()
         rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                 npairs, lut_p, _band_arg(band), _ptr(res), _ptr(ops), ops_cap)
+                                 npairs, lut_p, _band_arg(band), *extra, _ptr(res), _ptr(ops), ops_cap)
         self._check(rc, fn)
         return res[:npairs], ops
 
@@ -562,7 +605,7 @@ class Engine:
         """Banded affine score batch (sa_score_batch_banded_affine): the results array (start = -1, nops = 0)."""
         return self._score_banded_call("sa_score_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
 
-    def _score_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut):
+    def _score_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=()):
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
@@ -575,7 +618,7 @@ class Engine:
             lut_p = _ptr(lut)
         sc = scoring._c()
         rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                 npairs, lut_p, _band_arg(band), _ptr(res))
+                                 npairs, lut_p, _band_arg(band), *extra, _ptr(res))
         self._check(rc, fn)
         return res[:npairs]
 
@@ -1091,6 +1134,39 @@ class _Aligner:
         """The getScore() of every pair in one GPU pass with no traceback; getScore() afterwards is
         the last pair's.  band: as getAlignments (it raises on the Gotoh classes: getBandedScores)."""
         return [r.score for r in self._score_results(pairs, band)]
+
+
+    def _ends_free_check(self):
+        if self.ALGO not in (SA_NW, SA_HIRSCHBERG, SA_GLOBAL_GOTOH):
+            raise SeqalibError(f"{type(self).__name__} has no ends-free form: NeedlemanWunschSA, HirschbergSA (= NW) and GlobalGotohSA do")
+        if self.matrix is not None:
+            raise SeqalibError("a substitution matrix and free ends cannot be combined: the ends-free banded calls take match / mismatch scorings")
+
+    def getEndsFreeAlignments(self, pairs: Sequence[Tuple[object, object]], band: int, free_ends: int) -> List[AlignedSequence]:
+        """Semi-global banded alignments (sa_align_batch_banded_ends_free; NeedlemanWunschSA, HirschbergSA =
+        NW, GlobalGotohSA; the other aligners raise SeqalibError): the heads / tails named by free_ends
+        (an OR of SA_FREE_*) stay unaligned at no cost.  The aligned core comes from the ops; the free
+        ends are printed the way forceGlobal prints a local alignment's."""
+        self._ends_free_check()
+        res = _engine(self.device).align_banded_ends_free(self.ALGO, self.scoring, pairs, band, free_ends, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return [expand_ops(SA_SW, a, b, r, self.blank) for (a, b), r in zip(pairs, res)]   # (SA_SW: forceGlobal over (start, end))
+
+    def getEndsFreeAlignment(self, seq1, seq2, band: int, free_ends: int) -> AlignedSequence:
+        return self.getEndsFreeAlignments([(seq1, seq2)], band, free_ends)[0]
+
+    def _ends_free_score_results(self, pairs, band: int, free_ends: int) -> List[PairResult]:
+        self._ends_free_check()
+        res = _engine(self.device).score_banded_ends_free(self.ALGO, self.scoring, pairs, band, free_ends, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return res
+
+    def getEndsFreeScores(self, pairs: Sequence[Tuple[object, object]], band: int, free_ends: int) -> List[int]:
+        return [r.score for r in self._ends_free_score_results(pairs, band, free_ends)]
+
+    def getEndsFreeEndCells(self, pairs: Sequence[Tuple[object, object]], band: int, free_ends: int) -> List[Tuple[int, int]]:
+        """(end_i, end_j) of every pair: the last row-major candidate of the last row / column holding the maximum."""
+        return [(r.end_i, r.end_j) for r in self._ends_free_score_results(pairs, band, free_ends)]
 
 
 class _LocalAligner(_Aligner):

@@ -2348,6 +2348,8 @@ int sa_score_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
 // same batching with their own checks, the first kBandAffineVariants variants and 4-bit records.
 // sa_align_batch_banded_matrix / sa_score_batch_banded_matrix (banded_matrix_batch, below the matrix
 // calls) run it too, linear or affine by algorithm, on recoded sequences with the kMatchSub fills.
+// sa_align_batch_banded_ends_free / sa_score_batch_banded_ends_free (banded_ends_free_batch) run it with
+// the ends-free fills and walks (sa_banded_free.hip, sa_banded_affine_free.hip).
 
 // Algorithm, scoring and band checks shared with sa_banded_plan_query (c may be NULL).
 static int banded_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, uint32_t band) {
@@ -2420,16 +2422,19 @@ struct BandSub {
 // sub (the matrix band calls): the caller has run the algorithm, scoring and buffer checks, *sc holds
 // the table's extremes as match / mismatch with allow_mismatch = 1 (what banded_pair_plan bounds the
 // scores by), lut only labels, and the sequences are recoded on their way to the device.
+// free_ends >= 0 (the ends-free calls, algo SA_NW / SA_HIRSCHBERG or SA_GLOBAL_GOTOH): the SA_FREE_* bits
+// for the ends-free fills and walks; every check, the grouping and the launches are the global call's.
 static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                         const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
                         sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb, bool affine = false,
-                        const BandSub* sub = nullptr) {
+                        const BandSub* sub = nullptr, int free_ends = -1) {
     // (the checks that need no context come first, so they answer without a device too)
     int rc = sub ? SA_OK : affine ? banded_affine_prologue(c, algo, sc, band) : banded_prologue(c, &algo, sc, band);
     if (rc) return rc;
+    const bool ends_free = free_ends >= 0;
     const int nvariants = affine ? kBandAffineVariants : kBandVariants;
     auto rec_words = [&](const BandGeom& g, int v) { return affine ? band_affine_rec_words(g, v) : band_rec_words(g, v); };
-    if ((affine || sub) && off1 && off2) {   // the affine and matrix calls' per-pair limits answer without a context as well
+    if ((affine || sub || ends_free) && off1 && off2) {   // the affine, matrix and ends-free calls' per-pair limits answer without a context as well
         for (uint32_t p = 0; p < npairs; ++p) {
             if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
             BandGeom g;
@@ -2632,18 +2637,23 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         bp.L = kBandL[ln.v];
         bp.submat = sub ? dtab : nullptr;
         bp.sub_k = sub ? (uint32_t)sub->K : 0;
+        bp.free_ends = ends_free ? (uint32_t)free_ends : 0;
         BandAffineParams ap;
         static_cast<BandParams&>(ap) = bp;
         ap.gap_open = sc->gap_open;
         ap.gap_extend = sc->gap_extend;
         SA_HIP(c, hipEventRecord(ev[0], st));
         if (kev) SA_HIP(c, hipEventRecord(kev[0], st));
-        if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, mm, !notb, ap, st));
+        if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_fill(ln.v, use_lut, !notb, ap, st));
+        else if (ends_free) SA_HIP(c, launch_banded_free_fill(ln.v, use_lut, !notb, bp, st));
+        else if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, mm, !notb, ap, st));
         else SA_HIP(c, launch_banded_fill(algo, ln.v, mm, !notb, bp, st));
         if (kev) SA_HIP(c, hipEventRecord(kev[1], st));
         SA_HIP(c, hipEventRecord(ev[1], st));
         if (!notb) {
-            if (affine) SA_HIP(c, launch_banded_affine_tb(algo, use_lut, ap, st));
+            if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_tb(use_lut, ap, st));
+            else if (ends_free) SA_HIP(c, launch_banded_free_tb(use_lut, bp, st));
+            else if (affine) SA_HIP(c, launch_banded_affine_tb(algo, use_lut, ap, st));
             else SA_HIP(c, launch_banded_tb(algo, use_lut, bp, st));
             c->tb_kernels++;
         }
@@ -2726,6 +2736,32 @@ int sa_banded_affine_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32
     if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
     if (ws_bytes_per_pair) *ws_bytes_per_pair = band_affine_rec_words(g, v) * 4;
     return SA_OK;
+}
+
+// sa_align_batch_banded_ends_free / sa_score_batch_banded_ends_free: the algorithm picks the band (NW's
+// or GlobalGotoh's, whose prologues make the remaining checks), then banded_batch.
+static int banded_ends_free_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                  const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                                  uint32_t free_ends, sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
+    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
+    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
+    if (free_ends > 15) return fail(c, SA_ERR_ARG, "free_ends holds bits outside SA_FREE_*");
+    if (algo != SA_NW && algo != SA_HIRSCHBERG && algo != SA_GLOBAL_GOTOH)
+        return fail(c, SA_ERR_UNSUPPORTED, "ends-free banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only");
+    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, notb,
+                        algo == SA_GLOBAL_GOTOH, nullptr, (int)free_ends);
+}
+
+int sa_align_batch_banded_ends_free(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                    const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                                    uint32_t free_ends, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    return banded_ends_free_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, free_ends, results, ops, ops_cap, false);
+}
+
+int sa_score_batch_banded_ends_free(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                    const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
+                                    uint32_t free_ends, sa_result* results) {
+    return banded_ends_free_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, free_ends, results, nullptr, 0, true);
 }
 
 int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,

@@ -21,6 +21,14 @@
 // 3 M = Y, tested in that order), bit 2 "X = X(i-1, j) + extend" (tested before the open term, as the
 // walk does), bit 3 "Y = Y(i, j-1) + extend".  With gap_extend <= 0 these decide the walk (DESIGN.md
 // §2.13): it never needs a value.
+//
+// Ends-free mode (FREE, GlobalGotoh only; the sa_*_batch_banded_ends_free calls, instantiated by
+// sa_banded_affine_free.hip): as in sa_banded_fill.h.  BandParams::free_ends zeroes M on row 0
+// (SA_FREE_SEQ2_BEGIN) and column 0 (SA_FREE_SEQ1_BEGIN), X = Y = kBorderXY there as on every border; a
+// cell past the end of its diagonal keeps that diagonal's last M (EDGE steps only), and after the sweep
+// end_cell() takes the maximum of M over the last cells of the diagonals the END flags admit, keyed
+// (M << 32 | position).  The kernel's parameters are bools and shapes, and one more
+// would rename every existing kernel, so the mode travels as kMatchFreeBit in its match-mode value.
 #pragma once
 #include "sa_internal.h"
 
@@ -28,6 +36,7 @@ namespace sa {
 namespace {
 
 constexpr int32_t kBorderXY = -10000;   // X and Y of every border cell (the reference's constant)
+constexpr int kMatchFreeBit = 8;        // in the fill kernel's match-mode template value: the ends-free mode
 
 __device__ __forceinline__ int32_t aff_from_lower_lane(int32_t v) {   // lane l takes lane l - 1's, lane 0 kBandNeg
     return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x138, 0xf, 0xf, false);
@@ -36,8 +45,9 @@ __device__ __forceinline__ int32_t aff_from_upper_lane(int32_t v) {   // lane l 
     return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x130, 0xf, 0xf, false);
 }
 
-template <bool LOCAL, int R, int L, int MM, bool REC>
+template <bool LOCAL, int R, int L, int MM, bool REC, bool FREE>
 struct BandAffineFill {
+    static_assert(!(LOCAL && FREE), "the ends-free mode is GlobalGotoh's");
     static constexpr int S = R <= 8 ? 8 / R : 1;         // steps per record word
     static constexpr int WPS = R <= 8 ? 1 : R / 8;       // record words per step
     int32_t EM[R], EX[R], EY[R], OM[R], OX[R], OY[R];
@@ -46,7 +56,9 @@ struct BandAffineFill {
     int32_t goe, ge, gopen, match, mism;   // goe = gap_open + gap_extend
     const uint32_t* lut;
     const int16_t* sub;  // kMatchSub: the K x K table in LDS
-    long long best;      // local: (M << 32 | i * beff + c) of the last row-major maximum
+    long long best;      // local: (M << 32 | i * beff + c) of the last row-major maximum; ends-free: (M << 32 | position)
+    bool z_row0, z_col0; // ends-free: row 0 / column 0 hold M = 0 (a free begin)
+    int32_t imin, jmin;  // ends-free: candidates are (i, n) with i >= imin and (m, j) with j >= jmin
     int32_t score;       // global: M[m][n]
     uint32_t w[WPS];     // the step's 4-bit records
 
@@ -113,11 +125,14 @@ struct BandAffineFill {
                 interior = inb && (uint32_t)(i - 1) < (uint32_t)m && (uint32_t)(j - 1) < (uint32_t)n;
                 const bool border = inb && ((i == 0 && (uint32_t)j <= (uint32_t)n) || (j == 0 && (uint32_t)i <= (uint32_t)m));
                 const int32_t kk = i == 0 ? j : i;
-                const int32_t bval = LOCAL || kk == 0 ? 0 : (int32_t)((uint32_t)gopen + (uint32_t)kk * (uint32_t)ge);
-                vM = interior ? hv : border ? bval : kBandNeg;
+                const bool zero = LOCAL || kk == 0 || (FREE && (i == 0 ? z_row0 : z_col0));
+                const int32_t bval = zero ? 0 : (int32_t)((uint32_t)gopen + (uint32_t)kk * (uint32_t)ge);
+                // (ends-free: a cell past the end of its diagonal keeps the diagonal's last M)
+                const int32_t out = FREE && inb && (i > m || j > n) ? dg : kBandNeg;
+                vM = interior ? hv : border ? bval : out;
                 vX = interior ? x : border ? kBorderXY : kBandNeg;
                 vY = interior ? y : border ? kBorderXY : kBandNeg;
-                if (!LOCAL && inb && i == m && j == n) score = vM;
+                if (!LOCAL && !FREE && inb && i == m && j == n) score = vM;
             } else {
                 vM = inb ? hv : kBandNeg;
                 vX = inb ? x : kBandNeg;
@@ -140,11 +155,26 @@ struct BandAffineFill {
             if (REC) w[r / 8] |= code << (4 * (r & 7));
         }
     }
+
+    // Ends-free, after the sweep: the lane's maximum key over the last cells of its diagonals.
+    __device__ __forceinline__ void end_cell() {
+#pragma unroll
+        for (int x = 0; x < 2 * R; ++x) {
+            const int32_t c = 2 * l * R + x, k = lo + c;
+            const int32_t i = k <= n - m ? m : n - k, j = i + k;
+            const int32_t val = (x & 1) ? OM[x / 2] : EM[x / 2];
+            const bool cand = c < beff && (i == m ? j >= jmin : i >= imin);
+            const long long key = (long long)(((unsigned long long)(uint32_t)val << 32) | (uint32_t)(i == m ? m + j : i));
+            if (cand && key > best) best = key;
+        }
+    }
 };
 
-template <bool LOCAL, int R, int L, int MM, bool REC>
+template <bool LOCAL, int R, int L, int MMF, bool REC>   // MMF: the match mode [| kMatchFreeBit]
 __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams P) {
-    using F = BandAffineFill<LOCAL, R, L, MM, REC>;
+    constexpr int MM = MMF & ~kMatchFreeBit;
+    constexpr bool FREE = (MMF & kMatchFreeBit) != 0;
+    using F = BandAffineFill<LOCAL, R, L, MM, REC, FREE>;
     constexpr int PPW = 64 / L, S = F::S, WPS = F::WPS;
     __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
     if (MM == kMatchLut) {
@@ -189,8 +219,13 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
     f.mism = P.mismatch;
     f.lut = lut_s;
     f.sub = reinterpret_cast<const int16_t*>(lut_s);
-    f.best = (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
+    f.best = FREE ? LLONG_MIN : (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
     f.score = INT_MIN;
+    const uint32_t fe = FREE ? P.free_ends : 0u;
+    f.z_row0 = (fe & kFreeSeq2Begin) != 0;
+    f.z_col0 = (fe & kFreeSeq1Begin) != 0;
+    f.imin = (fe & kFreeSeq1End) ? 0 : f.m;
+    f.jmin = (fe & kFreeSeq2End) ? 0 : f.n;
     // steps without border cells and without cells outside the matrix: tA < t <= tB (idle lanes: all)
     int32_t tA = INT_MIN, tB = INT_MAX;
     if (live) {
@@ -291,7 +326,18 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
 
     // fold the pair's lanes
     int32_t sc_i = 0, sc_j = 0, sc = f.score;
-    if (!LOCAL) {
+    if (FREE) {   // (m, n) is a candidate of every pair, so b is a cell's key
+        f.end_cell();
+        long long b = f.best;
+        for (int off = L / 2; off >= 1; off >>= 1) {
+            const long long o = __shfl_xor(b, off);
+            b = o > b ? o : b;
+        }
+        sc = (int32_t)(b >> 32);
+        const int32_t pos = (int32_t)(uint32_t)b;
+        sc_i = pos < f.m ? pos : f.m;
+        sc_j = pos < f.m ? f.n : pos - f.m;
+    } else if (!LOCAL) {
         for (int off = L / 2; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
         sc_i = f.m;
         sc_j = f.n;

@@ -27,6 +27,20 @@
 // so the cell's term is one add and one 16-bit LDS read, and match / mism are not read.  A window
 // position outside its sequence holds 0 in every mode: entry 0 of the table (the host never passes
 // an empty one).
+//
+// Ends-free mode (ALG = kBandAlgFree, the sa_*_batch_banded_ends_free calls; instantiated by
+// sa_banded_free.hip): NW's cell, with BandParams::free_ends (wave-uniform) deciding two things.
+// Borders: row 0 holds 0 under SA_FREE_SEQ2_BEGIN and column 0 under SA_FREE_SEQ1_BEGIN, computed in
+// EDGE steps as every border value is.  End cell: every diagonal of the band ends in exactly one cell
+// of the last row (k <= n - m) or the last column (k >= n - m), and those cells are the candidates.
+// A cell past that end (i > m or j > n) is read by cells past the end only, so instead of kBandNeg it
+// keeps the value of the cell before it on its diagonal -- the `dg` the step holds anyway; such cells
+// are met in EDGE steps only, so the interior step is NW's, untouched, and tB stays NW's.  After the
+// sweep every register slot therefore holds its diagonal's last cell, and end_cell() takes the
+// maximum once per pair: a candidate's key is (H << 32 | position), position = i for (i, n) with
+// i < m and m + j for (m, j), so the signed 64-bit maximum is the last row-major maximum, for negative
+// H and border candidates alike (m = 0 or n = 0: every candidate is a border cell), within a lane and
+// across the pair's lanes.
 #pragma once
 #include "sa_internal.h"
 
@@ -42,6 +56,7 @@ __device__ __forceinline__ int32_t from_upper_lane(int32_t v) {   // lane l take
 
 template <int ALG, int R, int L, int MM, bool REC>
 struct BandFill {
+    static constexpr bool FREE = ALG == kBandAlgFree;
     static constexpr int S = R <= 16 ? 16 / R : 1;   // steps per record word
     int32_t E[R], O[R];
     uint32_t A[R], Bw[R + 1];
@@ -49,7 +64,9 @@ struct BandFill {
     int32_t G, match, mism;
     const uint32_t* lut;
     const int16_t* sub;  // kMatchSub: the K x K table in LDS
-    long long best;      // SW: (h << 32 | i * beff + c) of the last row-major maximum
+    long long best;      // SW: (h << 32 | i * beff + c) of the last row-major maximum; ends-free: (h << 32 | position)
+    int32_t g_row0, g_col0;   // ends-free: the border's gap per symbol in row 0 / column 0 (0 where the begin is free)
+    int32_t imin, jmin;       // ends-free: candidates are (i, n) with i >= imin and (m, j) with j >= jmin
     int32_t score;       // NW: H[m][n]
     uint32_t w0, w1;     // the step's 2-bit codes (w1: cells 16..31 of R = 32)
 
@@ -107,8 +124,12 @@ struct BandFill {
             if (EDGE) {
                 interior = inb && (uint32_t)(i - 1) < (uint32_t)m && (uint32_t)(j - 1) < (uint32_t)n;
                 const bool border = inb && ((i == 0 && (uint32_t)j <= (uint32_t)n) || (j == 0 && (uint32_t)i <= (uint32_t)m));
-                const int32_t bval = ALG == SA_NW ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)G) : 0;
-                val = interior ? hv : border ? bval : kBandNeg;
+                const int32_t bval = FREE           ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)(i == 0 ? g_row0 : g_col0))
+                                     : ALG == SA_NW ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)G)
+                                                    : 0;
+                // (ends-free: a cell past the end of its diagonal keeps the diagonal's last value)
+                const int32_t out = FREE && inb && (i > m || j > n) ? dg : kBandNeg;
+                val = interior ? hv : border ? bval : out;
                 if (ALG == SA_NW && inb && i == m && j == n) score = val;
             } else {
                 val = inb ? hv : kBandNeg;
@@ -124,6 +145,19 @@ struct BandFill {
                 if (r < 16) w0 |= code << (2 * (r & 15));
                 else w1 |= code << (2 * (r & 15));
             }
+        }
+    }
+
+    // Ends-free, after the sweep: the lane's maximum key over the last cells of its diagonals.
+    __device__ __forceinline__ void end_cell() {
+#pragma unroll
+        for (int x = 0; x < 2 * R; ++x) {
+            const int32_t c = 2 * l * R + x, k = lo + c;
+            const int32_t i = k <= n - m ? m : n - k, j = i + k;
+            const int32_t val = (x & 1) ? O[x / 2] : E[x / 2];
+            const bool cand = c < beff && (i == m ? j >= jmin : i >= imin);
+            const long long key = (long long)(((unsigned long long)(uint32_t)val << 32) | (uint32_t)(i == m ? m + j : i));
+            if (cand && key > best) best = key;
         }
     }
 };
@@ -173,8 +207,13 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
     f.mism = P.mismatch;
     f.lut = lut_s;
     f.sub = reinterpret_cast<const int16_t*>(lut_s);
-    f.best = (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
+    f.best = F::FREE ? LLONG_MIN : (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
     f.score = INT_MIN;
+    const uint32_t fe = F::FREE ? P.free_ends : 0u;
+    f.g_row0 = (fe & kFreeSeq2Begin) ? 0 : P.gap;
+    f.g_col0 = (fe & kFreeSeq1Begin) ? 0 : P.gap;
+    f.imin = (fe & kFreeSeq1End) ? 0 : f.m;
+    f.jmin = (fe & kFreeSeq2End) ? 0 : f.n;
     // steps without border cells and without cells outside the matrix: tA < t <= tB (idle lanes: all)
     int32_t tA = INT_MIN, tB = INT_MAX;
     if (live) {
@@ -280,6 +319,17 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         for (int off = L / 2; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
         sc_i = f.m;
         sc_j = f.n;
+    } else if (F::FREE) {   // (m, n) is a candidate of every pair, so b is a cell's key
+        f.end_cell();
+        long long b = f.best;
+        for (int off = L / 2; off >= 1; off >>= 1) {
+            const long long o = __shfl_xor(b, off);
+            b = o > b ? o : b;
+        }
+        sc = (int32_t)(b >> 32);
+        const int32_t pos = (int32_t)(uint32_t)b;
+        sc_i = pos < f.m ? pos : f.m;
+        sc_j = pos < f.m ? f.n : pos - f.m;
     } else {
         long long b = f.best;
         for (int off = L / 2; off >= 1; off >>= 1) {
@@ -332,6 +382,64 @@ hipError_t launch_band_fill_alg(int variant, bool rec, const BandParams& p, hipS
         case 7: return launch_band_fill_rl<ALG, 32, 64, MM>(rec, p, s);
     }
     return hipErrorInvalidValue;
+}
+
+// The walk: one lane per pair over the 2-bit records (0 stop, 1 diagonal, 2 up, 3 left).  Ends-free
+// (kBandAlgFree): it starts at the fill's end cell and stops at a border whose begin is free.
+template <int ALG, bool LUT>
+__global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
+    constexpr bool FREE = ALG == kBandAlgFree;
+    const uint32_t q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= P.count) return;
+    const uint32_t pair = P.idx[q];
+    const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
+    const int32_t m = (int32_t)(P.off1[pair + 1] - a1), n = (int32_t)(P.off2[pair + 1] - a2);
+    const uint8_t* s1 = P.seq1 + a1;
+    const uint8_t* s2 = P.seq2 + a2;
+    const BandGeom bg = band_geom(m, n, (int32_t)P.band);
+    const uint32_t* rec = P.rec + P.recoff[q];
+    sa_result* res = P.res + pair;
+    uint8_t* ops = P.ops + a1 + a2 + pair;
+    const int R = P.R, L = P.L, S = R <= 16 ? 16 / R : 1;
+    int32_t i = res->end_i, j = res->end_j;
+    if (ALG == SA_SW && (m == 0 || n == 0)) i = j = 0;
+    if (i < 0 || i > m || j < 0 || j > n) i = j = 0;   // (never: the fill's end cell is a cell)
+    uint32_t nops = 0;
+    while (i > 0 || j > 0) {
+        if (ALG == SA_SW) {
+            if (i == 0 || j == 0) break;
+        } else {
+            if (FREE && ((i == 0 && (P.free_ends & kFreeSeq2Begin)) || (j == 0 && (P.free_ends & kFreeSeq1Begin)))) break;
+            if (i == 0) { ops[nops++] = 'L'; --j; continue; }
+            if (j == 0) { ops[nops++] = 'U'; --i; continue; }
+        }
+        const int32_t tp = i + j - bg.lo - bg.tb, c = j - i - bg.lo;
+        if (c < 0 || c >= bg.beff) break;   // (never: the walk stays inside the band)
+        const int32_t l = c / (2 * R), rr = (c % (2 * R)) >> 1;
+        uint32_t w;
+        if (R <= 16) w = rec[(uint64_t)(tp / S) * L + l] >> (((tp % S) * R + rr) * 2);
+        else w = rec[((uint64_t)tp * 2 + (rr >> 4)) * L + l] >> ((rr & 15) * 2);
+        const uint32_t code = w & 3u;
+        if (code == 0) break;
+        if (code == 1) {
+            const uint32_t a = s1[i - 1], b = s2[j - 1];
+            const bool v = LUT ? ((P.lutbits[(a << 3) | (b >> 5)] >> (b & 31)) & 1u) != 0 : a == b;
+            ops[nops++] = (v || P.allow) ? (v ? 'M' : 'S') : 'X';
+            --i;
+            --j;
+        } else if (code == 2) {
+            ops[nops++] = 'U';
+            --i;
+        } else {
+            ops[nops++] = 'L';
+            --j;
+        }
+    }
+    res->start_i = i;
+    res->start_j = j;
+    res->nops = nops;
+    res->flags = 0;
+    res->reserved = 0;
 }
 
 }  // namespace

@@ -449,12 +449,23 @@ struct BandParams {
     // lutbits the label table over codes (the walk), match / mismatch are not read, allow = 1
     const int16_t* submat;
     uint32_t sub_k;
+    // the ends-free calls (sa_align_batch_banded_ends_free): the SA_FREE_* bits, the same for every pair
+    // of the launch; the other calls leave it 0 and their kernels do not read it.  (It takes what was
+    // the struct's tail padding: the kernel arguments keep their size and offsets.)
+    uint32_t free_ends;
 };
+static_assert(sizeof(BandParams) == 128, "free_ends fills the tail padding");
 // mm: kMatchEq, kMatchLut (lutbits) or kMatchSub (submat; instantiated in sa_banded_sub.hip /
 // sa_banded_affine_sub.hip, reached through these launchers)
 hipError_t launch_banded_fill(int algo, int variant, int mm, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_fill_sub(int algo, int variant, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_tb(int algo, bool lut, const BandParams& p, hipStream_t s);
+// The ends-free NW band (sa_banded_free.hip): the fill template's internal algorithm value (no public
+// algo: the calls take SA_NW / SA_HIRSCHBERG), its kMatchEq / kMatchLut fills and its walk.
+constexpr int kBandAlgFree = 100;
+constexpr uint32_t kFreeSeq1Begin = 1, kFreeSeq1End = 2, kFreeSeq2Begin = 4, kFreeSeq2End = 8;   // SA_FREE_*
+hipError_t launch_banded_free_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
+hipError_t launch_banded_free_tb(bool lut, const BandParams& p, hipStream_t s);
 
 // The banded affine path (sa_banded_affine.hip; sa_align_batch_banded_affine /
 // sa_score_batch_banded_affine): the first kBandAffineVariants entries of kBandR / kBandL, with three
@@ -478,4 +489,7 @@ struct BandAffineParams : BandParams {   // (gap is unused)
 hipError_t launch_banded_affine_fill(int algo, int variant, int mm, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_fill_sub(int algo, int variant, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_tb(int algo, bool lut, const BandAffineParams& p, hipStream_t s);
+// The ends-free GlobalGotoh band (sa_banded_affine_free.hip): kMatchEq / kMatchLut fills and the walk.
+hipError_t launch_banded_affine_free_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_free_tb(bool lut, const BandAffineParams& p, hipStream_t s);
 }  // namespace sa

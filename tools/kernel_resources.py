@@ -20,10 +20,14 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-devic
 NAME = re.compile(r"Function Name: _ZN2sa11fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
 FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
 BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d)ELb(\d)E")
-AFFINE = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb(\d)ELi(\d+)ELi(\d+)ELi(\d)ELb(\d)E")
+AFFINE = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb(\d)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
 SO2 = re.compile(r"Function Name: _ZN2sa15fill_so2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
 CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
+# the ends-free banded fills (sa_banded_free.hip, sa_banded_affine_free.hip): the linear fill's internal
+# algorithm value kBandAlgFree, and kMatchFreeBit in the affine fill's match-mode value
+BAND_ALG_FREE, MATCH_FREE_BIT = 100, 8
+FREE = {1: "NW free", 3: "GGotoh free"}
 MM = ["eq", "lut", "bits", "sub"]
 
 
@@ -44,13 +48,14 @@ def parse(text):
             continue
         m = BANDED.search(line)
         if m:   # the banded fills (sa_banded.hip): algorithm, R, L, match mode, REC
-            cur = {"banded": tuple(int(x) for x in m.groups())}
+            g = tuple(int(x) for x in m.groups())
+            cur = {"banded": ((1, 1) if g[0] == BAND_ALG_FREE else (g[0], 0)) + g[1:]}
             rows.append(cur)
             continue
         m = AFFINE.search(line)
         if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
-            cur = {"banded": (3 - g[0],) + g[1:]}
+            cur = {"banded": (3 - g[0], int(bool(g[3] & MATCH_FREE_BIT))) + g[1:3] + (g[3] & ~MATCH_FREE_BIT, g[4])}
             rows.append(cur)
             continue
         m = SO2.search(line)
@@ -90,8 +95,8 @@ def main(argv):
         print(f"{'banded':<8}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
         bad_banded = 0
         for r in banded:
-            alg, R, L, lut, rec = r["banded"]
-            print(f"{ALG[alg]:<8}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
+            alg, free, R, L, lut, rec = r["banded"]
+            print(f"{FREE[alg] if free else ALG[alg]:<8}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
                   f"{r['Occupancy']:>6}{r['LDS']:>7}")
             bad_banded += r["ScratchSize"] != 0
         print(f"# {len(banded)} banded kernels, {bad_banded} with scratch")
