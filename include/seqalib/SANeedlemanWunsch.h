@@ -66,6 +66,32 @@ public:
         return scoreBatch(pairs, seqalib::detail::band_of(band), (long long)freeEnds);
     }
 
+    // Extension: seeded ends-free banded NW (sa_align_batch_banded_seeded / sa_score_batch_banded_seeded): the
+    // ends-free forms above with pair p's band `band` diagonals either side of its seed diagonal diags[p]
+    // (k = j - i: a read, Seq1, that starts at position s of its window lies on k = s), so the band's width
+    // does not grow with the longer sequence.  std::runtime_error after setSubstitution(), when diags.size()
+    // is not pairs.size(), and for every status but SA_OK (a band with no legal begin or end among them),
+    // with the engine's message.
+    std::vector<AlignedSequence<Ty, Blank>> getAlignments(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          const std::vector<int32_t>& diags, size_t band, unsigned freeEnds) {
+        std::vector<sa_result> res;
+        auto out = seqalib::detail::run<SA_NW, NeedlemanWunschSA, ContainerType, Ty, Blank>(*this, pairs, res, seqalib::detail::band_of(band),
+                                                                                (long long)freeEnds, &diags);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+    std::vector<ScoreSystemType> getScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                           const std::vector<int32_t>& diags, size_t band, unsigned freeEnds) {
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_NW, NeedlemanWunschSA, ContainerType, Ty>(*this, pairs, res, seqalib::detail::band_of(band),
+                                                                       (long long)freeEnds, &diags);
+        std::vector<ScoreSystemType> out;
+        out.reserve(res.size());
+        for (auto& r : res) out.push_back(r.score);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+
     // Extension: H[m][n] of the last alignment.
     ScoreSystemType getScore() const { return LastScore; }
 

@@ -193,7 +193,7 @@ constexpr size_t kChunkPairs = SIZE_MAX;
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty, Ty Blank>
 std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
                                             std::vector<sa_result>& res, long long band = kNoBand,
-                                            long long free_ends = kNoFreeEnds) {
+                                            long long free_ends = kNoFreeEnds, const std::vector<int32_t>* diags = nullptr) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
@@ -224,7 +224,7 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
     // (a banded call is one range, and so is a matrix call)
     const size_t G = band == kNoBand && !sub && cp <= P / 2 ? (P + cp - 1) / cp : 1;
     if (G == 1) {
-        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub, free_ends);
+        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub, free_ends, diags);
         build_range(0, P);
         tm.lap("AlignedSequence lists");
         return out;
@@ -286,13 +286,15 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
 // buffers) over the batch; res[p] holds pair p's score and end cell.
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty>
 void run_scores(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
-                std::vector<sa_result>& res, long long band = kNoBand, long long free_ends = kNoFreeEnds) {
+                std::vector<sa_result>& res, long long band = kNoBand, long long free_ends = kNoFreeEnds,
+                const std::vector<int32_t>* diags = nullptr) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
     res.clear();
     const std::function<ScoreSystemType(Ty, Ty)>* sub = self.getSubstitution() ? &self.getSubstitution() : nullptr;
-    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub, free_ends);
+    diags_arg(diags, pairs.size(), free_ends);   // (a size mismatch throws for an empty batch too)
+    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub, free_ends, diags);
 }
 
 }  // namespace detail

@@ -406,6 +406,15 @@ inline uint32_t free_ends_arg(long long free_ends, long long band, bool sub) {
     if (free_ends > 0xffffffffLL) throw std::runtime_error("seqalib: freeEnds does not fit 32 bits");
     return (uint32_t)free_ends;
 }
+// diags (the seeded calls, sa_align_batch_banded_seeded / sa_score_batch_banded_seeded): one seed diagonal per
+// pair; they are ends-free calls, so free_ends is set too.
+inline const int32_t* diags_arg(const std::vector<int32_t>* diags, size_t npairs, long long free_ends) {
+    if (!diags) return nullptr;
+    if (free_ends == kNoFreeEnds) throw std::runtime_error("seqalib: seed diagonals need freeEnds");
+    if (diags->size() != npairs)
+        throw std::runtime_error("seqalib: " + std::to_string(diags->size()) + " seed diagonals for " + std::to_string(npairs) + " pairs");
+    return diags->data();
+}
 inline void banded_needs_table(bool overflow) {
     if (overflow)
         throw std::runtime_error("seqalib: banded calls take batches of at most " + std::to_string(kBandedMaxSymbols) +
@@ -446,8 +455,9 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
            std::vector<sa_result>& res, raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off,
            uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand, const SubFnTy* sub = nullptr,
-           long long free_ends = kNoFreeEnds) {
+           long long free_ends = kNoFreeEnds, const std::vector<int32_t>* diags = nullptr) {
     const uint32_t fe = free_ends == kNoFreeEnds ? 0 : free_ends_arg(free_ends, band, sub != nullptr);
+    const int32_t* dg = diags_arg(diags, pairs.size(), free_ends);
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -498,7 +508,12 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     ops_off.resize(n);
     for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
     tm.lap("match table + buffers");
-    if (free_ends != kNoFreeEnds) {
+    if (diags) {
+        check(sa_align_batch_banded_seeded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                           has_fn ? lut.data() : nullptr, dg, band_arg(band), fe, res.data(), ops.data(), cap),
+              "sa_align_batch_banded_seeded");
+        if (on_chunk && n) on_chunk(0, n);
+    } else if (free_ends != kNoFreeEnds) {
         check(sa_align_batch_banded_ends_free(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
                                               has_fn ? lut.data() : nullptr, band_arg(band), fe, res.data(), ops.data(), cap),
               "sa_align_batch_banded_ends_free");
@@ -539,8 +554,10 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
 template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubFnTy = std::function<int(Ty, Ty)>>
 void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
-           long long band = kNoBand, const SubFnTy* sub = nullptr, long long free_ends = kNoFreeEnds) {
+           long long band = kNoBand, const SubFnTy* sub = nullptr, long long free_ends = kNoFreeEnds,
+           const std::vector<int32_t>* diags = nullptr) {
     const uint32_t fe = free_ends == kNoFreeEnds ? 0 : free_ends_arg(free_ends, band, sub != nullptr);
+    const int32_t* dg = diags_arg(diags, pairs.size(), free_ends);
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -570,7 +587,11 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
         std::vector<uint8_t> lut;
         if (has_fn) lut = build_lut(coder, fn);
         const bool aff = banded_is_affine(algo);
-        if (free_ends != kNoFreeEnds)
+        if (diags)
+            check(sa_score_batch_banded_seeded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                               has_fn ? lut.data() : nullptr, dg, band_arg(band), fe, res.data()),
+                  "sa_score_batch_banded_seeded");
+        else if (free_ends != kNoFreeEnds)
             check(sa_score_batch_banded_ends_free(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
                                                   has_fn ? lut.data() : nullptr, band_arg(band), fe, res.data()),
                   "sa_score_batch_banded_ends_free");

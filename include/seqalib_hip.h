@@ -490,6 +490,65 @@ int sa_score_batch_banded_ends_free(sa_ctx* ctx, int algo, const sa_scoring* sco
                                     const uint8_t* match_lut, uint32_t band, uint32_t free_ends,
                                     sa_result* results);
 
+/* Seeded ends-free banded alignment: the ends-free calls above with every pair's band placed round a
+ * seed diagonal instead of the corner-to-corner corridor.  diag[p] = k_p is the seed diagonal of pair p
+ * (k = j - i: a read, Seq1, that starts at position s of its window, Seq2, lies on k = s); band = w is
+ * the same for every pair.
+ * Band.  lo = k_p - w, hi = k_p + w, clipped to the matrix as everywhere: lo' = max(lo, -m),
+ *   hi' = min(hi, n), B' = hi' - lo' + 1 <= 2w + 1 diagonals.  The window length does not enter the
+ *   band's width, so a short read can go against a whole contig (n < 2^24) and two long reads that
+ *   overlap by little need no wide band.
+ * Algorithms.  SA_NW (SA_HIRSCHBERG means NW): 2-bit records, B' <= 4096.  SA_GLOBAL_GOTOH: 4-bit
+ *   records, B' <= 2048.
+ * Semantics.  Exactly those of sa_align_batch_banded_ends_free with this band in place of its band:
+ *   the borders, "a term that would read a cell outside the band is no candidate", the end-cell rule
+ *   (the last candidate in row-major order holding the maximum), the walk with its stop rules, tie order
+ *   and op codes, and the score contract for the score call.  (0, 0) and (m, n) need not be in the band,
+ *   which changes two things:
+ *   A legal begin must exist in the band: lo' <= 0 <= hi' (the cell (0, 0)), or SA_FREE_SEQ2_BEGIN and
+ *     hi' >= 0 (a row-0 cell), or SA_FREE_SEQ1_BEGIN and lo' <= 0 (a column-0 cell).
+ *   A legal end must exist in the band: lo' <= n - m <= hi' (the cell (m, n)), or SA_FREE_SEQ2_END and
+ *     lo' <= n - m (a last-row cell), or SA_FREE_SEQ1_END and hi' >= n - m (a last-column cell).
+ *   A pair that lacks either answers SA_ERR_UNSUPPORTED with a message naming the pair and the missing
+ *   end.  Under this rule a border cell whose begin is not free is in the band only when (0, 0) is, so
+ *   "in-band border cells keep k * gap" is exactly the DP restricted to the band; (m, n) is a candidate
+ *   only when it is in the band.
+ * Equivalences.
+ *   (a) With w >= m + n every result field and op equals sa_align_batch_banded_ends_free's with a
+ *       whole-matrix band.
+ *   (b) When n - m is even, diag = (n - m) / 2 and w' = w + |n - m| / 2: the call at w' equals the
+ *       ends-free call at w in every field and op (n == m: diag = 0 and the same w).
+ *   (c) For a fixed diag the score does not fall as w grows.
+ * Status codes (all checked before the context is looked at, so a NULL context gives the same answer;
+ * a NULL context with valid arguments: SA_ERR_ARG):
+ *   diag NULL with npairs > 0; diag[p] outside [-m_p, n_p] (the seed diagonal does not cross the matrix;
+ *   the message names the pair); free_ends > 15; an invalid algo; band >= 2^31: SA_ERR_ARG.
+ *   SA_SW, SA_LOCAL_GOTOH, SA_MYERS_MILLER: SA_ERR_UNSUPPORTED.
+ *   Everything else as the ends-free calls: the 2^29 score bound per pair, m, n < 2^24, gap_extend <= 0
+ *   for GlobalGotoh, band == 0 needs allow_mismatch, B' above 4096 / 2048: SA_ERR_UNSUPPORTED;
+ *   SA_ERR_CAPACITY; SA_ERR_NOMEM.
+ * Records (align call): tend - tb + 1 steps per pair with
+ *   tb = (max(-lo', 0) + max(-hi', 0)) & ~1 and tend = min(m + n, 2m + hi', 2n - lo') - lo',
+ *   about 2 min(m, n) + 2w steps whatever the longer sequence's length.  Launch splitting under
+ *   sa_set_workspace_limit, the joining of neighbouring variants ($SEQALIB_BAND_MERGE), sa_last_timings
+ *   and sa_last_plan_ex (SA_KERNEL_BANDED, the widest variant's cells per lane, 1 wave,
+ *   SA_RECORDS_BAND2 / BAND4 / NONE) work as for the banded calls.
+ * sa_banded_seeded_plan_query (host-only): variant, pairs per wave and record bytes of one shape, or the
+ *   status the calls give it (SA_ERR_UNSUPPORTED for an illegal band).  sa_banded_plan_query and
+ *   sa_banded_affine_plan_query describe the corridor band and do not apply. */
+int sa_align_batch_banded_seeded(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const uint8_t* match_lut, const int32_t* diag, uint32_t band, uint32_t free_ends,
+                                 sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_banded_seeded(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const uint8_t* match_lut, const int32_t* diag, uint32_t band, uint32_t free_ends,
+                                 sa_result* results);
+int sa_banded_seeded_plan_query(int algo, uint64_t m, uint64_t n, int32_t diag, uint32_t band, uint32_t free_ends,
+                                int* cells_per_lane, int* pairs_per_wave, uint64_t* ws_bytes_per_pair);
+
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events
  * recorded on the stream they ran on: total fill-kernel ms, total traceback-kernel ms, and the
  * number of fill launches.  Waits for those events. */

@@ -163,6 +163,12 @@ def load_library():
                                                   C.c_uint32, C.c_uint32, vp, vp, C.c_uint64]
     L.sa_score_batch_banded_ends_free.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
                                                   C.c_uint32, C.c_uint32, vp]
+    L.sa_align_batch_banded_seeded.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
+                                               C.c_uint32, C.c_uint32, vp, vp, C.c_uint64]
+    L.sa_score_batch_banded_seeded.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp, vp,
+                                               C.c_uint32, C.c_uint32, vp]
+    L.sa_banded_seeded_plan_query.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32,
+                                              i32p, i32p, u64p]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
     L.sa_last_kernel_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sa_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p, u64p]
@@ -185,6 +191,7 @@ def load_library():
                "sa_align_batch_matrix", "sa_score_batch_matrix", "sa_matrix_plan_query",
                "sa_align_batch_banded_matrix", "sa_score_batch_banded_matrix",
                "sa_align_batch_banded_ends_free", "sa_score_batch_banded_ends_free",
+               "sa_align_batch_banded_seeded", "sa_score_batch_banded_seeded", "sa_banded_seeded_plan_query",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -347,6 +354,18 @@ def _free_ends_arg(free_ends) -> int:
     if free_ends < 0 or free_ends > 0xFFFFFFFF:
         raise SeqalibError(f"free_ends must be an OR of SA_FREE_*: {free_ends}")
     return free_ends
+
+
+def _diag_arg(diag, npairs: int) -> np.ndarray:
+    try:
+        d = np.asarray(diag, dtype=np.int64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise SeqalibError(f"diag must be an array of integers: {e}")
+    if len(d) != npairs:
+        raise SeqalibError(f"diag holds {len(d)} seed diagonals for {npairs} pairs")
+    if d.size and (d.min() < -(2 ** 31) or d.max() >= 2 ** 31):
+        raise SeqalibError("a seed diagonal does not fit 32 bits")
+    return np.ascontiguousarray(d, dtype=np.int32)
 
 
 def _as_bytes(s) -> bytes:
@@ -576,7 +595,39 @@ class Engine:
         s1, off1, s2, off2 = pack_pairs(pairs)
         return self._score_results(self.score_banded_ends_free_packed(algo, scoring, s1, off1, s2, off2, band, free_ends, lut))
 
-    def _align_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=()):
+    def align_banded_seeded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, diag, band: int, free_ends: int,
+                                   lut: Optional[np.ndarray] = None):
+        """Seeded ends-free banded host-buffer batch (sa_align_batch_banded_seeded): the ends-free call with
+        pair p's band `band` diagonals either side of its seed diagonal diag[p] (k = j - i; an int32 array
+        of npairs).  Returns (results, ops) as align_packed."""
+        d = _diag_arg(diag, len(off1) - 1)
+        return self._align_banded_call("sa_align_batch_banded_seeded", algo, scoring, s1, off1, s2, off2, band, lut,
+                                       (_free_ends_arg(free_ends),), (_ptr(d),))
+
+    def score_banded_seeded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, diag, band: int, free_ends: int,
+                                   lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Seeded ends-free banded score batch (sa_score_batch_banded_seeded): the results array (start = -1, nops = 0)."""
+        d = _diag_arg(diag, len(off1) - 1)
+        return self._score_banded_call("sa_score_batch_banded_seeded", algo, scoring, s1, off1, s2, off2, band, lut,
+                                       (_free_ends_arg(free_ends),), (_ptr(d),))
+
+    def align_banded_seeded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], diag,
+                            band: int, free_ends: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the seeded banded call."""
+        def call(algo, scoring, s1, off1, s2, off2, band, lut):
+            return self.align_banded_seeded_packed(algo, scoring, s1, off1, s2, off2, diag, band, free_ends, lut)
+        return self._align_banded_pairs(call, algo, scoring, pairs, band, lut)
+
+    def score_banded_seeded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], diag,
+                            band: int, free_ends: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the seeded banded call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_banded_seeded_packed(algo, scoring, s1, off1, s2, off2, diag, band, free_ends, lut))
+
+    # pre: the call's arguments between match_lut and band (the seeded calls' diag); extra: those after band
+    def _align_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=(), pre=()):
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
@@ -591,7 +642,7 @@ class Engine:
             lut_p = _ptr(lut)
         sc = scoring._c()
         rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                 npairs, lut_p, _band_arg(band), *extra, _ptr(res), _ptr(ops), ops_cap)
+                                 npairs, lut_p, *pre, _band_arg(band), *extra, _ptr(res), _ptr(ops), ops_cap)
         self._check(rc, fn)
         return res[:npairs], ops
 
@@ -605,7 +656,7 @@ class Engine:
         """Banded affine score batch (sa_score_batch_banded_affine): the results array (start = -1, nops = 0)."""
         return self._score_banded_call("sa_score_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
 
-    def _score_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=()):
+    def _score_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=(), pre=()):
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
@@ -618,7 +669,7 @@ class Engine:
             lut_p = _ptr(lut)
         sc = scoring._c()
         rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                 npairs, lut_p, _band_arg(band), *extra, _ptr(res))
+                                 npairs, lut_p, *pre, _band_arg(band), *extra, _ptr(res))
         self._check(rc, fn)
         return res[:npairs]
 
@@ -984,6 +1035,19 @@ def banded_affine_plan_query(algo: int, max_m: int, max_n: int, band: int, npair
     return R.value, ppw.value, ws.value
 
 
+def banded_seeded_plan_query(algo: int, m: int, n: int, diag: int, band: int, free_ends: int):
+    """(cells per lane and step, pairs per wave, record bytes) of the seeded banded calls for one pair of
+    m x n seeded at diagonal `diag` (sa_banded_seeded_plan_query).  Raises where the calls refuse the shape:
+    a diagonal outside the matrix, a band with no legal begin or end, a band wider than the path holds."""
+    L = load_library()
+    R, ppw, ws = C.c_int(), C.c_int(), C.c_uint64()
+    rc = L.sa_banded_seeded_plan_query(algo, m, n, int(diag), _band_arg(band), _free_ends_arg(free_ends),
+                                       C.byref(R), C.byref(ppw), C.byref(ws))
+    if rc:
+        raise SeqalibError(f"sa_banded_seeded_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
+    return R.value, ppw.value, ws.value
+
+
 def matrix_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 20):
     """(kernel, R, W, workspace bytes per pair) of sa_align_batch_matrix for a batch of this shape with
     nsym distinct symbols (sa_matrix_plan_query; no GPU needed)."""
@@ -1167,6 +1231,40 @@ class _Aligner:
     def getEndsFreeEndCells(self, pairs: Sequence[Tuple[object, object]], band: int, free_ends: int) -> List[Tuple[int, int]]:
         """(end_i, end_j) of every pair: the last row-major candidate of the last row / column holding the maximum."""
         return [(r.end_i, r.end_j) for r in self._ends_free_score_results(pairs, band, free_ends)]
+
+
+    def _seeded_check(self, pairs, diags):
+        if self.ALGO not in (SA_NW, SA_HIRSCHBERG, SA_GLOBAL_GOTOH):
+            raise SeqalibError(f"{type(self).__name__} has no seeded form: NeedlemanWunschSA, HirschbergSA (= NW) and GlobalGotohSA do")
+        if self.matrix is not None:
+            raise SeqalibError("a substitution matrix and a seeded band cannot be combined: the seeded banded calls take match / mismatch scorings")
+        return _diag_arg(diags, len(pairs))
+
+    def getSeededAlignments(self, pairs: Sequence[Tuple[object, object]], diags, band: int, free_ends: int) -> List[AlignedSequence]:
+        """getEndsFreeAlignments with pair p's band `band` diagonals either side of its seed diagonal
+        diags[p] (k = j - i; sa_align_batch_banded_seeded), so the band's width does not grow with the
+        longer sequence.  NeedlemanWunschSA, HirschbergSA = NW, GlobalGotohSA; the other aligners raise
+        SeqalibError, as does a diags of another length than pairs."""
+        d = self._seeded_check(pairs, diags)
+        res = _engine(self.device).align_banded_seeded(self.ALGO, self.scoring, pairs, d, band, free_ends, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return [expand_ops(SA_SW, a, b, r, self.blank) for (a, b), r in zip(pairs, res)]   # (SA_SW: forceGlobal over (start, end))
+
+    def getSeededAlignment(self, seq1, seq2, diag: int, band: int, free_ends: int) -> AlignedSequence:
+        return self.getSeededAlignments([(seq1, seq2)], [diag], band, free_ends)[0]
+
+    def _seeded_score_results(self, pairs, diags, band: int, free_ends: int) -> List[PairResult]:
+        d = self._seeded_check(pairs, diags)
+        res = _engine(self.device).score_banded_seeded(self.ALGO, self.scoring, pairs, d, band, free_ends, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return res
+
+    def getSeededScores(self, pairs: Sequence[Tuple[object, object]], diags, band: int, free_ends: int) -> List[int]:
+        return [r.score for r in self._seeded_score_results(pairs, diags, band, free_ends)]
+
+    def getSeededEndCells(self, pairs: Sequence[Tuple[object, object]], diags, band: int, free_ends: int) -> List[Tuple[int, int]]:
+        """(end_i, end_j) of every pair, as getEndsFreeEndCells."""
+        return [(r.end_i, r.end_j) for r in self._seeded_score_results(pairs, diags, band, free_ends)]
 
 
 class _LocalAligner(_Aligner):

@@ -2378,36 +2378,61 @@ static int banded_affine_prologue(sa_ctx* c, int algo, const sa_scoring* sc, uin
     return SA_OK;
 }
 
+// The seeded calls' band of one pair (seed NULL: the corridor band of every other call).
+struct BandSeed {
+    int32_t diag;        // the seed diagonal, -m <= diag <= n (checked by the caller)
+    uint32_t free_ends;
+    uint64_t pair;       // for the message
+};
+
+// The seeded legality rule: the band must hold a legal begin and a legal end (include/seqalib_hip.h).
+static int banded_seed_legal(sa_ctx* c, const BandSeed& sd, const BandGeom& g, int64_t m, int64_t n) {
+    const bool begin = (g.lo <= 0 && 0 <= g.hi) || ((sd.free_ends & kFreeSeq2Begin) && g.hi >= 0) ||
+                       ((sd.free_ends & kFreeSeq1Begin) && g.lo <= 0);
+    const int64_t d = n - m;
+    const bool end = (g.lo <= d && d <= g.hi) || ((sd.free_ends & kFreeSeq2End) && g.lo <= d) ||
+                     ((sd.free_ends & kFreeSeq1End) && g.hi >= d);
+    if (begin && end) return SA_OK;
+    return fail(c, SA_ERR_UNSUPPORTED,
+                "pair " + std::to_string(sd.pair) + ": the band [" + std::to_string(g.lo) + ", " + std::to_string(g.hi) +
+                    "] holds no legal " + (begin ? "end" : end ? "begin" : "begin and no legal end") +
+                    " under free_ends = " + std::to_string(sd.free_ends));
+}
+
 // One pair's geometry and fill variant, or why the banded path does not take it.
 static int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t m, uint64_t n, uint32_t band,
-                            BandGeom* g, int* variant) {
+                            BandGeom* g, int* variant, const BandSeed* seed = nullptr) {
     if (m >= (1u << 24) || n >= (1u << 24)) return fail(c, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
     auto a = [](int32_t x) { return (int64_t)(x < 0 ? -(int64_t)x : x); };
+    auto geom = [&]() {
+        const int32_t w = (int32_t)std::min(band, kBandMaxW);
+        return seed ? band_geom_seeded((int32_t)m, (int32_t)n, w, seed->diag) : band_geom((int32_t)m, (int32_t)n, w);
+    };
     if (algo == SA_LOCAL_GOTOH || algo == SA_GLOBAL_GOTOH) {   // (the linear calls never get here with these)
         const int64_t big = std::max(std::max(a(sc->gap_open) + a(sc->gap_extend), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
         if ((int64_t)(m + n + 1) * big + 10000 >= kBandScoreLimit)
             return fail(c, SA_ERR_UNSUPPORTED,
                         "banded affine calls need (m + n + 1) * max(|gap_open| + |gap_extend|, |match|, |mismatch|) + 10000 < 2^29");
-        *g = band_geom((int32_t)m, (int32_t)n, (int32_t)std::min(band, kBandMaxW));
+        *g = geom();
         *variant = band_affine_variant(g->beff);
         if (*variant < 0)
             return fail(c, SA_ERR_UNSUPPORTED, "band of " + std::to_string(g->beff) + " diagonals inside the matrix exceeds the " +
                                                    std::to_string(kBandAffineMaxDiagonals) + " one wave holds with three values per cell");
         if (algo == SA_LOCAL_GOTOH && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
             return fail(c, SA_ERR_UNSUPPORTED, "banded LocalGotoh needs (m + 1) * band diagonals < 2^31");
-        return SA_OK;
+        return seed ? banded_seed_legal(c, *seed, *g, (int64_t)m, (int64_t)n) : SA_OK;
     }
     const int64_t big = std::max(std::max(a(sc->gap), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
     if ((int64_t)(m + n + 1) * big >= kBandScoreLimit)
         return fail(c, SA_ERR_UNSUPPORTED, "banded calls need (m + n + 1) * max(|gap|, |match|, |mismatch|) < 2^29");
-    *g = band_geom((int32_t)m, (int32_t)n, (int32_t)std::min(band, kBandMaxW));
+    *g = geom();
     *variant = band_variant(g->beff);
     if (*variant < 0)
         return fail(c, SA_ERR_UNSUPPORTED, "band of " + std::to_string(g->beff) + " diagonals inside the matrix exceeds the " +
                                                std::to_string(kBandMaxDiagonals) + " one wave holds");
     if (algo == SA_SW && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
         return fail(c, SA_ERR_UNSUPPORTED, "banded SW needs (m + 1) * band diagonals < 2^31");
-    return SA_OK;
+    return seed ? banded_seed_legal(c, *seed, *g, (int64_t)m, (int64_t)n) : SA_OK;
 }
 
 // A matrix band call's recode (banded_matrix_batch): the batch's K used symbols in byte order, their
@@ -2424,14 +2449,21 @@ struct BandSub {
 // scores by), lut only labels, and the sequences are recoded on their way to the device.
 // free_ends >= 0 (the ends-free calls, algo SA_NW / SA_HIRSCHBERG or SA_GLOBAL_GOTOH): the SA_FREE_* bits
 // for the ends-free fills and walks; every check, the grouping and the launches are the global call's.
+// diag (the seeded calls, with free_ends >= 0; the caller has checked -m <= diag[p] <= n): every pair's
+// band lies round its seed diagonal, and the seeded fills and walks (sa_banded_seeded.hip,
+// sa_banded_affine_seeded.hip) read the diagonals from behind each launch's idx entries.
 static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                         const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
                         sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb, bool affine = false,
-                        const BandSub* sub = nullptr, int free_ends = -1) {
+                        const BandSub* sub = nullptr, int free_ends = -1, const int32_t* diag = nullptr) {
     // (the checks that need no context come first, so they answer without a device too)
     int rc = sub ? SA_OK : affine ? banded_affine_prologue(c, algo, sc, band) : banded_prologue(c, &algo, sc, band);
     if (rc) return rc;
     const bool ends_free = free_ends >= 0;
+    auto pair_plan = [&](uint32_t p, BandGeom* g, int* v) {
+        const BandSeed sd{diag ? diag[p] : 0, (uint32_t)(ends_free ? free_ends : 0), p};
+        return banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, g, v, diag ? &sd : nullptr);
+    };
     const int nvariants = affine ? kBandAffineVariants : kBandVariants;
     auto rec_words = [&](const BandGeom& g, int v) { return affine ? band_affine_rec_words(g, v) : band_rec_words(g, v); };
     if ((affine || sub || ends_free) && off1 && off2) {   // the affine, matrix and ends-free calls' per-pair limits answer without a context as well
@@ -2439,7 +2471,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
             if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
             BandGeom g;
             int v = 0;
-            if ((rc = banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, &g, &v))) return rc;
+            if ((rc = pair_plan(p, &g, &v))) return rc;
         }
     }
     if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
@@ -2462,7 +2494,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     for (uint32_t p = 0; p < npairs; ++p) {
         BandGeom g;
         int v = 0;
-        if ((rc = banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, &g, &v))) return rc;
+        if ((rc = pair_plan(p, &g, &v))) return rc;
         words[p] = notb ? 0 : rec_words(g, v);
         bucket[v].push_back(p);
     }
@@ -2491,7 +2523,8 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
             bool fits = true;
             for (size_t k = 0; k < bucket[v].size() && !notb && fits; ++k) {
                 const uint32_t p = bucket[v][k];
-                const BandGeom g = band_geom((int32_t)(off1[p + 1] - off1[p]), (int32_t)(off2[p + 1] - off2[p]), (int32_t)w);
+                const int32_t pm = (int32_t)(off1[p + 1] - off1[p]), pn = (int32_t)(off2[p + 1] - off2[p]);
+                const BandGeom g = diag ? band_geom_seeded(pm, pn, (int32_t)w, diag[p]) : band_geom(pm, pn, (int32_t)w);
                 moved[k] = rec_words(g, v + 1);
                 fits = moved[k] <= budget_words;
             }
@@ -2539,6 +2572,17 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         launches.push_back(cur);
     }
     if (!notb && (rc = ensure_ws(c, std::max<uint64_t>(ws_words * 4, 256)))) return rc;
+    // seeded: each launch's block of the uploaded array is [its idx entries][their diagonals]
+    const uint32_t idx_stride = diag ? 2 : 1;
+    if (diag) {
+        std::vector<uint32_t> both;
+        both.reserve(2ull * npairs);
+        for (const Launch& ln : launches) {
+            both.insert(both.end(), idx.begin() + ln.first, idx.begin() + ln.first + ln.count);
+            for (uint32_t k = 0; k < ln.count; ++k) both.push_back((uint32_t)diag[idx[ln.first + k]]);
+        }
+        idx.swap(both);
+    }
 
     const bool use_lut = lut && !lut_is_identity(lut);
     std::vector<uint32_t> bits;
@@ -2556,7 +2600,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     }
     auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
     const uint64_t b_s1 = al(t1 + 1), b_s2 = al(t2 + 1), b_o = al(8ull * (npairs + 1)), b_res = al(sizeof(sa_result) * (uint64_t)npairs);
-    const uint64_t b_ops = al(ops_total + 1), b_bits = al(8192), b_idx = al(4ull * npairs), b_ro = al(8ull * npairs);
+    const uint64_t b_ops = al(ops_total + 1), b_bits = al(8192), b_idx = al(4ull * idx.size()), b_ro = al(8ull * npairs);
     const uint64_t b_tab = sub ? al(2ull * kSubMaxSyms * kSubMaxSyms) : 0;
     if ((rc = ensure_io(c, b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_bits + b_idx + b_ro + b_tab))) return rc;
     uint8_t* q = c->io;
@@ -2589,7 +2633,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     SA_HIP(c, hipMemcpyAsync(do1, off1, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
     SA_HIP(c, hipMemcpyAsync(do2, off2, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
     if (use_lut) SA_HIP(c, hipMemcpyAsync(dbits, bits.data(), 8192, hipMemcpyHostToDevice, st));
-    SA_HIP(c, hipMemcpyAsync(didx, idx.data(), 4ull * npairs, hipMemcpyHostToDevice, st));
+    SA_HIP(c, hipMemcpyAsync(didx, idx.data(), 4ull * idx.size(), hipMemcpyHostToDevice, st));
     SA_HIP(c, hipMemcpyAsync(dro, recoff.data(), 8ull * npairs, hipMemcpyHostToDevice, st));
 
     const bool kernel_timing = getenv("SEQALIB_KERNEL_TIMING") != nullptr;
@@ -2622,7 +2666,7 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         bp.seq2 = d2;
         bp.off2 = do2;
         bp.lutbits = use_lut ? dbits : nullptr;
-        bp.idx = didx + ln.first;
+        bp.idx = didx + (uint64_t)idx_stride * ln.first;
         bp.recoff = dro + ln.first;
         bp.rec = reinterpret_cast<uint32_t*>(c->ws);
         bp.res = dres;
@@ -2644,14 +2688,18 @@ static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
         ap.gap_extend = sc->gap_extend;
         SA_HIP(c, hipEventRecord(ev[0], st));
         if (kev) SA_HIP(c, hipEventRecord(kev[0], st));
-        if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_fill(ln.v, use_lut, !notb, ap, st));
+        if (diag && affine) SA_HIP(c, launch_banded_affine_seeded_fill(ln.v, use_lut, !notb, ap, st));
+        else if (diag) SA_HIP(c, launch_banded_seeded_fill(ln.v, use_lut, !notb, bp, st));
+        else if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_fill(ln.v, use_lut, !notb, ap, st));
         else if (ends_free) SA_HIP(c, launch_banded_free_fill(ln.v, use_lut, !notb, bp, st));
         else if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, mm, !notb, ap, st));
         else SA_HIP(c, launch_banded_fill(algo, ln.v, mm, !notb, bp, st));
         if (kev) SA_HIP(c, hipEventRecord(kev[1], st));
         SA_HIP(c, hipEventRecord(ev[1], st));
         if (!notb) {
-            if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_tb(use_lut, ap, st));
+            if (diag && affine) SA_HIP(c, launch_banded_affine_seeded_tb(use_lut, ap, st));
+            else if (diag) SA_HIP(c, launch_banded_seeded_tb(use_lut, bp, st));
+            else if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_tb(use_lut, ap, st));
             else if (ends_free) SA_HIP(c, launch_banded_free_tb(use_lut, bp, st));
             else if (affine) SA_HIP(c, launch_banded_affine_tb(algo, use_lut, ap, st));
             else SA_HIP(c, launch_banded_tb(algo, use_lut, bp, st));
@@ -2762,6 +2810,75 @@ int sa_score_batch_banded_ends_free(sa_ctx* c, int algo, const sa_scoring* sc, c
                                     const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
                                     uint32_t free_ends, sa_result* results) {
     return banded_ends_free_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, free_ends, results, nullptr, 0, true);
+}
+
+// sa_align_batch_banded_seeded / sa_score_batch_banded_seeded: the ends-free calls with every pair's band
+// round its seed diagonal.  Their own prologue (what the seed adds), then banded_batch, whose per-pair
+// plan applies the legality rule.
+static int banded_seeded_prologue(sa_ctx* c, int algo, const sa_scoring* sc, uint32_t band, uint32_t free_ends) {
+    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
+    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
+    if (free_ends > 15) return fail(c, SA_ERR_ARG, "free_ends holds bits outside SA_FREE_*");
+    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: 2 * band + 1 diagonals overflow 32 bits");
+    if (algo != SA_NW && algo != SA_HIRSCHBERG && algo != SA_GLOBAL_GOTOH)
+        return fail(c, SA_ERR_UNSUPPORTED, "seeded banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only");
+    return SA_OK;
+}
+
+static int banded_seed_in_matrix(sa_ctx* c, uint64_t pair, uint64_t m, uint64_t n, int32_t diag) {
+    if ((int64_t)diag < -(int64_t)m || (int64_t)diag > (int64_t)n)
+        return fail(c, SA_ERR_ARG, "pair " + std::to_string(pair) + ": seed diagonal " + std::to_string(diag) +
+                                       " does not cross the " + std::to_string(m) + " x " + std::to_string(n) + " matrix");
+    return SA_OK;
+}
+
+static int banded_seeded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                               const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
+                               const int32_t* diag, uint32_t band, uint32_t free_ends, sa_result* results, uint8_t* ops,
+                               uint64_t ops_cap, bool notb) {
+    int rc = banded_seeded_prologue(c, algo, sc, band, free_ends);
+    if (rc) return rc;
+    if (npairs && !diag) return fail(c, SA_ERR_ARG, "diag is NULL");
+    if (off1 && off2) {
+        for (uint32_t p = 0; p < npairs; ++p) {
+            if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
+            if ((rc = banded_seed_in_matrix(c, p, off1[p + 1] - off1[p], off2[p + 1] - off2[p], diag[p]))) return rc;
+        }
+    }
+    static const int32_t none = 0;   // (npairs == 0: banded_batch still takes the seeded route)
+    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, notb,
+                        algo == SA_GLOBAL_GOTOH, nullptr, (int)free_ends, diag ? diag : &none);
+}
+
+int sa_align_batch_banded_seeded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
+                                 const int32_t* diag, uint32_t band, uint32_t free_ends, sa_result* results, uint8_t* ops,
+                                 uint64_t ops_cap) {
+    return banded_seeded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, diag, band, free_ends, results, ops, ops_cap, false);
+}
+
+int sa_score_batch_banded_seeded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
+                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
+                                 const int32_t* diag, uint32_t band, uint32_t free_ends, sa_result* results) {
+    return banded_seeded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, diag, band, free_ends, results, nullptr, 0, true);
+}
+
+int sa_banded_seeded_plan_query(int algo, uint64_t m, uint64_t n, int32_t diag, uint32_t band, uint32_t free_ends,
+                                int* cells_per_lane, int* pairs_per_wave, uint64_t* ws_bytes_per_pair) {
+    const sa_scoring any{0, 0, 0, 0, 0, 1};   // (as sa_banded_plan_query: the scoring-dependent checks are the calls')
+    int rc = banded_seeded_prologue(nullptr, algo, &any, band, free_ends);
+    if (rc) return rc;
+    if (m >= (1u << 24) || n >= (1u << 24)) return fail(nullptr, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
+    if ((rc = banded_seed_in_matrix(nullptr, 0, m, n, diag))) return rc;
+    const bool affine = algo == SA_GLOBAL_GOTOH;
+    const BandSeed sd{diag, free_ends, 0};
+    BandGeom g;
+    int v = 0;
+    if ((rc = banded_pair_plan(nullptr, affine ? algo : SA_NW, &any, m, n, band, &g, &v, &sd))) return rc;
+    if (cells_per_lane) *cells_per_lane = kBandR[v];
+    if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
+    if (ws_bytes_per_pair) *ws_bytes_per_pair = (affine ? band_affine_rec_words(g, v) : band_rec_words(g, v)) * 4;
+    return SA_OK;
 }
 
 int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,

@@ -29,6 +29,9 @@
 // end_cell() takes the maximum of M over the last cells of the diagonals the END flags admit, keyed
 // (M << 32 | position).  The kernel's parameters are bools and shapes, and one more
 // would rename every existing kernel, so the mode travels as kMatchFreeBit in its match-mode value.
+//
+// Seeded mode (kMatchSeedBit beside kMatchFreeBit; the sa_*_batch_banded_seeded calls, instantiated by
+// sa_banded_affine_seeded.hip): the ends-free mode with band_geom_seeded, as in sa_banded_fill.h.
 #pragma once
 #include "sa_internal.h"
 
@@ -37,6 +40,7 @@ namespace {
 
 constexpr int32_t kBorderXY = -10000;   // X and Y of every border cell (the reference's constant)
 constexpr int kMatchFreeBit = 8;        // in the fill kernel's match-mode template value: the ends-free mode
+constexpr int kMatchSeedBit = 16;       // with kMatchFreeBit: the seeded band (band_geom_seeded, diagonals behind idx)
 
 __device__ __forceinline__ int32_t aff_from_lower_lane(int32_t v) {   // lane l takes lane l - 1's, lane 0 kBandNeg
     return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x138, 0xf, 0xf, false);
@@ -170,10 +174,11 @@ struct BandAffineFill {
     }
 };
 
-template <bool LOCAL, int R, int L, int MMF, bool REC>   // MMF: the match mode [| kMatchFreeBit]
+template <bool LOCAL, int R, int L, int MMF, bool REC>   // MMF: the match mode [| kMatchFreeBit [| kMatchSeedBit]]
 __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams P) {
-    constexpr int MM = MMF & ~kMatchFreeBit;
-    constexpr bool FREE = (MMF & kMatchFreeBit) != 0;
+    constexpr int MM = MMF & ~(kMatchFreeBit | kMatchSeedBit);
+    constexpr bool FREE = (MMF & kMatchFreeBit) != 0, SEEDED = (MMF & kMatchSeedBit) != 0;
+    static_assert(FREE || !SEEDED, "the seeded band is an ends-free one");
     using F = BandAffineFill<LOCAL, R, L, MM, REC, FREE>;
     constexpr int PPW = 64 / L, S = F::S, WPS = F::WPS;
     __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
@@ -206,7 +211,8 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
         f.n = (int32_t)(P.off2[pair + 1] - a2);
         s1 += a1;
         s2 += a2;
-        bg = band_geom(f.m, f.n, (int32_t)P.band);
+        bg = SEEDED ? band_geom_seeded(f.m, f.n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+                    : band_geom(f.m, f.n, (int32_t)P.band);
     }
     f.lo = bg.lo;
     f.beff = bg.beff;

@@ -41,6 +41,19 @@
 // i < m and m + j for (m, j), so the signed 64-bit maximum is the last row-major maximum, for negative
 // H and border candidates alike (m = 0 or n = 0: every candidate is a border cell), within a lane and
 // across the pair's lanes.
+//
+// Seeded mode (ALG = kBandAlgSeeded, the sa_*_batch_banded_seeded calls; instantiated by
+// sa_banded_seeded.hip): the ends-free mode with the pair's band placed round its seed diagonal
+// (band_geom_seeded; the diagonal is read from behind the launch's idx entries).  Nothing else differs:
+// t, c, the windows and end_cell() are written in lo' / hi'.  tA: a step t > max(hi', -lo') - lo' has
+// t - c >= 2 (i >= 1) and t + c + 2 lo' >= 2 (j >= 1) for every c = t (mod 2) in [0, B'), whatever the
+// signs of lo' and hi' -- a band that begins on row 0 (lo' > 0) has tA = hi' - lo', one that begins on
+// column 0 (hi' < 0) tA = -2 lo'.  tB: a step t <= min(2m, 2n - hi' - lo') has i <= m (t - c <= 2m) and
+// j <= n (t + c + 2 lo' <= 2n) for every such c, for a band that ends on the last row (hi' < n - m) or
+// the last column (lo' > n - m) alike.  Steps before a pair's tb (another pair of the wave begins
+// earlier) hold cells with i < 0 or j < 0 only, which stay kBandNeg.  (m, n) is a candidate only when
+// n - m is in the band, which `j >= jmin` / `i >= imin` say already.  The host admits a pair only if a
+// legal begin and a candidate exist, so `best` leaves LLONG_MIN.
 #pragma once
 #include "sa_internal.h"
 
@@ -56,7 +69,7 @@ __device__ __forceinline__ int32_t from_upper_lane(int32_t v) {   // lane l take
 
 template <int ALG, int R, int L, int MM, bool REC>
 struct BandFill {
-    static constexpr bool FREE = ALG == kBandAlgFree;
+    static constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded;
     static constexpr int S = R <= 16 ? 16 / R : 1;   // steps per record word
     int32_t E[R], O[R];
     uint32_t A[R], Bw[R + 1];
@@ -196,7 +209,8 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         f.n = (int32_t)(P.off2[pair + 1] - a2);
         s1 += a1;
         s2 += a2;
-        bg = band_geom(f.m, f.n, (int32_t)P.band);
+        bg = ALG == kBandAlgSeeded ? band_geom_seeded(f.m, f.n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+                                   : band_geom(f.m, f.n, (int32_t)P.band);
     }
     f.lo = bg.lo;
     f.beff = bg.beff;
@@ -319,7 +333,7 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         for (int off = L / 2; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
         sc_i = f.m;
         sc_j = f.n;
-    } else if (F::FREE) {   // (m, n) is a candidate of every pair, so b is a cell's key
+    } else if (F::FREE) {   // (m, n) is a candidate of every pair (seeded: the host admits a pair with a candidate only), so b is a cell's key
         f.end_cell();
         long long b = f.best;
         for (int off = L / 2; off >= 1; off >>= 1) {
@@ -388,7 +402,7 @@ hipError_t launch_band_fill_alg(int variant, bool rec, const BandParams& p, hipS
 // (kBandAlgFree): it starts at the fill's end cell and stops at a border whose begin is free.
 template <int ALG, bool LUT>
 __global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
-    constexpr bool FREE = ALG == kBandAlgFree;
+    constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded;
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= P.count) return;
     const uint32_t pair = P.idx[q];
@@ -396,7 +410,8 @@ __global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
     const int32_t m = (int32_t)(P.off1[pair + 1] - a1), n = (int32_t)(P.off2[pair + 1] - a2);
     const uint8_t* s1 = P.seq1 + a1;
     const uint8_t* s2 = P.seq2 + a2;
-    const BandGeom bg = band_geom(m, n, (int32_t)P.band);
+    const BandGeom bg = ALG == kBandAlgSeeded ? band_geom_seeded(m, n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+                                              : band_geom(m, n, (int32_t)P.band);
     const uint32_t* rec = P.rec + P.recoff[q];
     sa_result* res = P.res + pair;
     uint8_t* ops = P.ops + a1 + a2 + pair;

@@ -411,6 +411,23 @@ __host__ __device__ inline BandGeom band_geom(int32_t m, int32_t n, int32_t w) {
     if (hi > n) hi = n;
     return BandGeom{lo, hi, hi - lo + 1, (-lo) & ~1, m + n - lo};
 }
+// The seeded band (sa_align_batch_banded_seeded): w diagonals either side of the seed diagonal k,
+// -m <= k <= n, clipped to the matrix as above.  (0, 0) and (m, n) need not be in it, so tb and tend
+// take their general forms, of which band_geom's are the case lo' <= 0 <= hi', lo' <= n - m <= hi':
+// the first step holding a cell is that of (0, lo') when lo' >= 0 (t = 0), of (0, 0) when the band
+// straddles diagonal 0 (t = -lo') and of (-hi', 0) when hi' < 0 (t = -hi' - lo'); the last one is that
+// of (m, n) when n - m is in the band, else of the last cell of diagonal hi' (hi' < n - m: (m, m + hi'))
+// or lo' (lo' > n - m: (n - lo', n)).
+__host__ __device__ inline BandGeom band_geom_seeded(int32_t m, int32_t n, int32_t w, int32_t k) {
+    int32_t lo = k - w, hi = k + w;
+    if (lo < -m) lo = -m;
+    if (hi > n) hi = n;
+    const int32_t tb = ((lo < 0 ? -lo : 0) + (hi < 0 ? -hi : 0)) & ~1;
+    int32_t last = m + n;
+    if (2 * m + hi < last) last = 2 * m + hi;
+    if (2 * n - lo < last) last = 2 * n - lo;
+    return BandGeom{lo, hi, hi - lo + 1, tb, last - lo};
+}
 // Fill variants: R cells per lane and step, L lanes per pair (64 / L pairs per wave); a variant holds
 // bands of up to 2 R L diagonals.  kBandMaxDiagonals is the widest (clipped) band the path takes.
 constexpr int kBandVariants = 8;
@@ -466,6 +483,12 @@ constexpr int kBandAlgFree = 100;
 constexpr uint32_t kFreeSeq1Begin = 1, kFreeSeq1End = 2, kFreeSeq2Begin = 4, kFreeSeq2End = 8;   // SA_FREE_*
 hipError_t launch_banded_free_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_free_tb(bool lut, const BandParams& p, hipStream_t s);
+// The seeded ends-free NW band (sa_banded_seeded.hip; sa_align_batch_banded_seeded): kBandAlgFree's fill
+// and walk with band_geom_seeded.  BandParams is full, so the seed diagonals travel behind the launch's
+// idx entries: idx[count + q] is the diagonal (an int32) of the pair idx[q].  Only these kernels read it.
+constexpr int kBandAlgSeeded = 101;
+hipError_t launch_banded_seeded_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
+hipError_t launch_banded_seeded_tb(bool lut, const BandParams& p, hipStream_t s);
 
 // The banded affine path (sa_banded_affine.hip; sa_align_batch_banded_affine /
 // sa_score_batch_banded_affine): the first kBandAffineVariants entries of kBandR / kBandL, with three
@@ -492,4 +515,8 @@ hipError_t launch_banded_affine_tb(int algo, bool lut, const BandAffineParams& p
 // The ends-free GlobalGotoh band (sa_banded_affine_free.hip): kMatchEq / kMatchLut fills and the walk.
 hipError_t launch_banded_affine_free_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_free_tb(bool lut, const BandAffineParams& p, hipStream_t s);
+// The seeded ends-free GlobalGotoh band (sa_banded_affine_seeded.hip): the same with the diagonals
+// behind idx, as above.
+hipError_t launch_banded_affine_seeded_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_seeded_tb(bool lut, const BandAffineParams& p, hipStream_t s);
 }  // namespace sa

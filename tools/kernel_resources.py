@@ -26,8 +26,12 @@ CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
 # the ends-free banded fills (sa_banded_free.hip, sa_banded_affine_free.hip): the linear fill's internal
 # algorithm value kBandAlgFree, and kMatchFreeBit in the affine fill's match-mode value
+# the seeded fills (sa_banded_seeded.hip, sa_banded_affine_seeded.hip): kBandAlgSeeded, and kMatchSeedBit beside
+# kMatchFreeBit
 BAND_ALG_FREE, MATCH_FREE_BIT = 100, 8
+BAND_ALG_SEEDED, MATCH_SEED_BIT = 101, 16
 FREE = {1: "NW free", 3: "GGotoh free"}
+SEEDED = {1: "NW seeded", 3: "GGotoh seeded"}
 MM = ["eq", "lut", "bits", "sub"]
 
 
@@ -49,13 +53,14 @@ def parse(text):
         m = BANDED.search(line)
         if m:   # the banded fills (sa_banded.hip): algorithm, R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
-            cur = {"banded": ((1, 1) if g[0] == BAND_ALG_FREE else (g[0], 0)) + g[1:]}
+            cur = {"banded": ((1, 1) if g[0] == BAND_ALG_FREE else (1, 2) if g[0] == BAND_ALG_SEEDED else (g[0], 0)) + g[1:]}
             rows.append(cur)
             continue
         m = AFFINE.search(line)
         if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
-            cur = {"banded": (3 - g[0], int(bool(g[3] & MATCH_FREE_BIT))) + g[1:3] + (g[3] & ~MATCH_FREE_BIT, g[4])}
+            mode = 2 if g[3] & MATCH_SEED_BIT else int(bool(g[3] & MATCH_FREE_BIT))
+            cur = {"banded": (3 - g[0], mode) + g[1:3] + (g[3] & ~(MATCH_FREE_BIT | MATCH_SEED_BIT), g[4])}
             rows.append(cur)
             continue
         m = SO2.search(line)
@@ -92,11 +97,12 @@ def main(argv):
         if not rows and not banded:
             return 0
     if banded:
-        print(f"{'banded':<8}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
+        wide = 14 if any(r["banded"][1] == 2 for r in banded) else 8
+        print(f"{'banded':<{wide}}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
         bad_banded = 0
         for r in banded:
             alg, free, R, L, lut, rec = r["banded"]
-            print(f"{FREE[alg] if free else ALG[alg]:<8}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
+            print(f"{SEEDED[alg] if free == 2 else FREE[alg] if free else ALG[alg]:<{wide}}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
                   f"{r['Occupancy']:>6}{r['LDS']:>7}")
             bad_banded += r["ScratchSize"] != 0
         print(f"# {len(banded)} banded kernels, {bad_banded} with scratch")
