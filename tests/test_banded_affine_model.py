@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from banded_affine_model import GLOBAL, LOCAL, affine_rescore, banded_affine_model
-from util import LG_HACK_SIZES, oracle_align
+from util import LG_HACK_SIZES, REGIME_AFFINE_BANDED, oracle_align
 
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 SCORINGS = [(-3, -1, 1, -1), (0, -1, 1, -1), (-4, 0, 2, -1), (2, -2, 1, -1), (-3, -1, 2, -1, False)]
@@ -37,11 +37,31 @@ def model_pairs():
 PAIRS = model_pairs()
 
 
+def regime_pairs():
+    """Ten pairs up to 90 long for the regime scorings (util.REGIME_AFFINE_BANDED): the edge shapes and
+    related pairs, long enough for the -10000 border to win a cell under gap terms in the thousands."""
+    rng = np.random.default_rng(17)
+    pairs = [(b"", b""), (b"", b"ACGT"), (b"ACGT", b""), (b"A", b"A"), (b"A", b"C")]
+    for m, n in ((7, 9), (33, 31), (64, 70), (90, 88), (75, 12)):
+        a = ACGT[rng.integers(0, 4, m)].tobytes()
+        b = bytearray((a + ACGT[rng.integers(0, 4, n)].tobytes())[:n])
+        for q in rng.integers(0, n, n // 5):
+            b[q] = ACGT[rng.integers(0, 4)]
+        pairs.append((a, bytes(b)))
+    return pairs
+
+
+REGIME_PAIRS = regime_pairs()
+
+
 @pytest.mark.parametrize("algo", [GLOBAL, LOCAL])
-@pytest.mark.parametrize("args", SCORINGS)
+@pytest.mark.parametrize("args", SCORINGS + REGIME_AFFINE_BANDED)
 def test_whole_matrix_band_is_the_oracle(algo, args):
-    assert not any((len(a), len(b)) in LG_HACK_SIZES for a, b in PAIRS)
-    for p, (a, b) in enumerate(PAIRS):
+    """SCORINGS on the 60 pairs; the regime scorings (gap_open of either sign, gap_extend = 0,
+    match <= 0, mismatch >= match, gap terms in the thousands) on REGIME_PAIRS."""
+    pairs = PAIRS if args in SCORINGS else REGIME_PAIRS
+    assert not any((len(a), len(b)) in LG_HACK_SIZES for a, b in pairs)
+    for p, (a, b) in enumerate(pairs):
         o = oracle_align(algo, args, a, b)
         assert o["rc"] == 0
         want = (o["score"], o["end_i"], o["end_j"], o["start_i"], o["start_j"], o["ops"])

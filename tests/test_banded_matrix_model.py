@@ -10,6 +10,7 @@ from banded_affine_model import banded_affine_model
 from banded_matrix_model import GLOBAL_GOTOH, LOCAL_GOTOH, NW, SW, banded_matrix_model
 from submat_model import model_align
 from test_gpu_banded import banded_model
+from util import REGIME_AFFINE_BANDED, REGIME_LINEAR, scoring_fields
 
 FIELDS = ("score", "end_i", "end_j", "start_i", "start_j", "ops")
 ABC = np.frombuffer(b"ABC", dtype=np.uint8)
@@ -74,6 +75,44 @@ def test_two_valued_table_is_the_affine_banded_model(algo, args):
     for p, (a, b) in enumerate(PAIRS3 + PAIRS20):
         for w in (0, 1, 3, 16):
             assert banded_matrix_model(algo, (go, ge), S, a, b, w) == banded_affine_model(algo, args, a, b, w), (p, w)
+
+
+def regime_pairs():
+    """Nine pairs: the empty and one-symbol shapes, two over ABC and two over the twenty letters."""
+    return PAIRS3[:5] + [PAIRS3[8], PAIRS3[13], PAIRS20[10], PAIRS20[15]]
+
+
+def regime_scorings(algo):
+    """The regime scorings, gap_extend <= 0, with mismatches allowed (a table scores every cell): one that
+    forbids them is taken with its mismatch value allowed, the two-argument ones (no mismatch value) are
+    left out -- their gap terms, 0 and 1, come with other scorings."""
+    out = []
+    for s in (REGIME_LINEAR if algo in (SW, NW) else REGIME_AFFINE_BANDED):
+        if len(s) >= 3 and s[:3 if algo in (SW, NW) else 4] not in out:
+            out.append(s[:3 if algo in (SW, NW) else 4])
+    return out
+
+
+def test_regime_gap_terms():
+    assert {s[0] for s in regime_scorings(NW)} == {-4097, -4096, -700, -3, -2, -1, 0, 1, 2}
+    assert {s[:2] for s in regime_scorings(GLOBAL_GOTOH)} == {(-6000, -5000), (-2049, -513), (-2048, -512), (-3, -5), (-3, -1),
+                                                             (-3, 0), (0, -2), (0, -1), (0, 0), (1, -1), (2, -1)}
+
+
+@pytest.mark.parametrize("algo", [SW, NW, LOCAL_GOTOH, GLOBAL_GOTOH])
+def test_two_valued_table_is_the_banded_model_under_the_regime_scorings(algo):
+    """The degenerate table S[a][b] = (a == b ? match : mismatch) gives the model without a table under
+    every regime scoring that allows mismatches: gap terms 0, > 0 and in the thousands, match <= 0,
+    mismatch >= match; and no assertion of either model's walk fires."""
+    for args in regime_scorings(algo):
+        g, ma, mi, go, ge, _ = scoring_fields(args)
+        S = lambda a, b: ma if a == b else mi
+        for p, (a, b) in enumerate(regime_pairs()):
+            for w in (0, 1, 3, 100):
+                if algo in (SW, NW):
+                    assert banded_matrix_model(algo, g, S, a, b, w) == banded_model(algo, args, a, b, w), (args, p, w)
+                else:
+                    assert banded_matrix_model(algo, (go, ge), S, a, b, w) == banded_affine_model(algo, args, a, b, w), (args, p, w)
 
 
 def test_labels_follow_the_match_function():

@@ -11,7 +11,7 @@ from banded_affine_model import affine_rescore
 from ends_free_model import ends_free_model
 from seeded_model import (GLOBAL_GOTOH, NW, SEQ1_BEGIN, SEQ1_END, SEQ2_BEGIN, SEQ2_END, seeded_band, seeded_legal,
                           seeded_model)
-from util import linear_rescore, scoring_fields
+from util import REGIME_AFFINE_BANDED, REGIME_LINEAR, linear_rescore, scoring_fields
 
 LINEAR = [(-1, 1, -1), (-2, 2, -3), (0, 1, -1), (-1, -1, -2)]          # gap <= 0
 AFFINE = [(-3, -1, 1, -1), (-2, 0, 2, -3), (1, -1, 1, -1), (0, 0, 1, -2)]   # extend <= 0, open + extend <= 0
@@ -77,6 +77,31 @@ def test_the_corridor_seed_is_the_ends_free_model():
         got = seeded_model(algo, args, a, b, d // 2, w + abs(d) // 2, fe)
         assert got == ends_free_model(algo, args, a, b, w, fe), (algo, args, a, b, w, fe)
         done += 1
+
+
+REGIME = [(NW, s) for s in REGIME_LINEAR] + [(GLOBAL_GOTOH, s) for s in REGIME_AFFINE_BANDED]
+
+
+@pytest.mark.parametrize("algo,args", REGIME, ids=lambda v: "_".join(str(int(x)) for x in v) if isinstance(v, tuple) else str(v))
+def test_the_equivalences_hold_under_the_regime_scorings(algo, args):
+    """Equivalences (a) and (b) under every scoring of util.REGIME_LINEAR / REGIME_AFFINE_BANDED: gap
+    terms 0 and > 0, in the thousands, match <= 0, mismatch >= match.  (Without mismatches a band of one
+    diagonal has no candidate, so w' >= 1 there.)"""
+    rng = np.random.default_rng(7)
+    wmin = 0 if scoring_fields(args)[5] else 1
+    done = 0
+    while done < 24:
+        a, b = _seq(rng, b"ACG", int(rng.integers(0, 15))), _seq(rng, b"ACG", int(rng.integers(0, 15)))
+        d = len(b) - len(a)
+        fe = int(rng.integers(0, 16))
+        whole = len(a) + len(b) + 1
+        k = int(rng.integers(-len(a), len(b) + 1))
+        assert seeded_model(algo, args, a, b, k, whole, fe) == ends_free_model(algo, args, a, b, whole, fe), (a, b, k, fe)
+        if d % 2 == 0:
+            w = int(rng.integers(wmin, 7))
+            got = seeded_model(algo, args, a, b, d // 2, w + abs(d) // 2, fe)
+            assert got == ends_free_model(algo, args, a, b, w, fe), (a, b, w, fe)
+            done += 1
 
 
 def test_the_score_does_not_fall_as_the_band_grows():

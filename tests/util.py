@@ -51,6 +51,10 @@ REGIME_AFFINE = [   # LocalGotoh, GlobalGotoh, Myers-Miller
 # the one regime scoring under which the reference's LocalGotoh walk may not terminate (the oracle
 # returns rc == -3, the engine sets SA_FLAG_DIVERGED)
 REGIME_DIVERGING = (2, (-3, 1, 1, -1, True))
+# what the banded affine, banded matrix, ends-free and seeded calls take: gap_extend <= 0 (they refuse
+# (-3, 1, 1, -1) with SA_ERR_UNSUPPORTED: test_banded_affine_abi.py)
+REGIME_AFFINE_BANDED = [s for s in REGIME_AFFINE if s[1] <= 0]
+assert len(REGIME_AFFINE_BANDED) == 23 and set(REGIME_AFFINE) - set(REGIME_AFFINE_BANDED) == {REGIME_DIVERGING[1]}
 LG_HACK_SIZES = ((314, 288), (60, 57), (61, 58))   # SALocalGotoh.h:484-488
 
 
