@@ -368,6 +368,10 @@ def _diag_arg(diag, npairs: int) -> np.ndarray:
     return np.ascontiguousarray(d, dtype=np.int32)
 
 
+def _lut_arg(lut) -> Optional[np.ndarray]:
+    return None if lut is None else np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
+
+
 def _as_bytes(s) -> bytes:
     if isinstance(s, (bytes, bytearray)):
         return bytes(s)
@@ -557,14 +561,14 @@ class Engine:
                             s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None):
         """Banded host-buffer batch (sa_align_batch_banded): NW / SW over the cells within `band`
         diagonals of each pair's corner-to-corner corridor.  Returns (results, ops) as align_packed."""
-        return self._align_banded_call("sa_align_batch_banded", algo, scoring, s1, off1, s2, off2, band, lut)
+        return self._banded_call("sa_align_batch_banded", algo, scoring, s1, off1, s2, off2, band, lut)
 
     def align_banded_affine_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                                    s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None):
         """Banded affine host-buffer batch (sa_align_batch_banded_affine): LocalGotoh / GlobalGotoh over
         the cells within `band` diagonals of each pair's corridor, raw path (no LocalGotoh size hack).
         Returns (results, ops) as align_packed."""
-        return self._align_banded_call("sa_align_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
+        return self._banded_call("sa_align_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
 
     def align_banded_ends_free_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                                       s2: np.ndarray, off2: np.ndarray, band: int, free_ends: int,
@@ -572,15 +576,15 @@ class Engine:
         """Ends-free banded host-buffer batch (sa_align_batch_banded_ends_free): banded NW (SA_NW,
         SA_HIRSCHBERG) or banded GlobalGotoh in which the heads / tails named by `free_ends` (an OR of
         SA_FREE_*) stay unaligned at no cost.  Returns (results, ops) as align_packed."""
-        return self._align_banded_call("sa_align_batch_banded_ends_free", algo, scoring, s1, off1, s2, off2, band, lut,
+        return self._banded_call("sa_align_batch_banded_ends_free", algo, scoring, s1, off1, s2, off2, band, lut,
                                        (_free_ends_arg(free_ends),))
 
     def score_banded_ends_free_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                                       s2: np.ndarray, off2: np.ndarray, band: int, free_ends: int,
                                       lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Ends-free banded score batch (sa_score_batch_banded_ends_free): the results array (start = -1, nops = 0)."""
-        return self._score_banded_call("sa_score_batch_banded_ends_free", algo, scoring, s1, off1, s2, off2, band, lut,
-                                       (_free_ends_arg(free_ends),))
+        return self._banded_call("sa_score_batch_banded_ends_free", algo, scoring, s1, off1, s2, off2, band, lut,
+                                       (_free_ends_arg(free_ends),), with_ops=False)
 
     def align_banded_ends_free(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
                                free_ends: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
@@ -602,7 +606,7 @@ class Engine:
         pair p's band `band` diagonals either side of its seed diagonal diag[p] (k = j - i; an int32 array
         of npairs).  Returns (results, ops) as align_packed."""
         d = _diag_arg(diag, len(off1) - 1)
-        return self._align_banded_call("sa_align_batch_banded_seeded", algo, scoring, s1, off1, s2, off2, band, lut,
+        return self._banded_call("sa_align_batch_banded_seeded", algo, scoring, s1, off1, s2, off2, band, lut,
                                        (_free_ends_arg(free_ends),), (_ptr(d),))
 
     def score_banded_seeded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
@@ -610,8 +614,8 @@ class Engine:
                                    lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Seeded ends-free banded score batch (sa_score_batch_banded_seeded): the results array (start = -1, nops = 0)."""
         d = _diag_arg(diag, len(off1) - 1)
-        return self._score_banded_call("sa_score_batch_banded_seeded", algo, scoring, s1, off1, s2, off2, band, lut,
-                                       (_free_ends_arg(free_ends),), (_ptr(d),))
+        return self._banded_call("sa_score_batch_banded_seeded", algo, scoring, s1, off1, s2, off2, band, lut,
+                                       (_free_ends_arg(free_ends),), (_ptr(d),), with_ops=False)
 
     def align_banded_seeded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], diag,
                             band: int, free_ends: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
@@ -626,52 +630,43 @@ class Engine:
         s1, off1, s2, off2 = pack_pairs(pairs)
         return self._score_results(self.score_banded_seeded_packed(algo, scoring, s1, off1, s2, off2, diag, band, free_ends, lut))
 
-    # pre: the call's arguments between match_lut and band (the seeded calls' diag); extra: those after band
-    def _align_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=(), pre=()):
+    def _packed_call(self, fn, algo, scoring, s1, off1, s2, off2, mid, with_ops):
+        """One host-buffer batch call of the banded / matrix families.  mid: the entry point's arguments
+        between npairs and results, in order (an array passes as its address, None as NULL); with_ops:
+        an align call, which returns (results, ops) -- a score call returns the results alone."""
         npairs = len(off1) - 1
         s1 = np.ascontiguousarray(s1, dtype=np.uint8)
         s2 = np.ascontiguousarray(s2, dtype=np.uint8)
         off1 = np.ascontiguousarray(off1, dtype=np.uint64)
         off2 = np.ascontiguousarray(off2, dtype=np.uint64)
-        ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
         res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
-        ops = np.zeros(ops_cap, dtype=np.uint8)
-        lut_p = 0
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
-            lut_p = _ptr(lut)
+        out = [_ptr(res)]
+        if with_ops:
+            ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
+            ops = np.zeros(ops_cap, dtype=np.uint8)
+            out += [_ptr(ops), ops_cap]
+        # (mid itself stays bound until the call has returned: it is what keeps converted copies alive)
+        ptrs = [0 if a is None else _ptr(a) if isinstance(a, np.ndarray) else a for a in mid]
         sc = scoring._c()
         rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                 npairs, lut_p, *pre, _band_arg(band), *extra, _ptr(res), _ptr(ops), ops_cap)
+                                 npairs, *ptrs, *out)
         self._check(rc, fn)
-        return res[:npairs], ops
+        return (res[:npairs], ops) if with_ops else res[:npairs]
+
+    # pre: the call's arguments between match_lut and band (the seeded calls' diag); extra: those after band
+    def _banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=(), pre=(), with_ops=True):
+        return self._packed_call(fn, algo, scoring, s1, off1, s2, off2,
+                                 (_lut_arg(lut), *pre, _band_arg(band), *extra), with_ops)
 
     def score_banded_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                             s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Banded score batch (sa_score_batch_banded): the results array (start = -1, nops = 0)."""
-        return self._score_banded_call("sa_score_batch_banded", algo, scoring, s1, off1, s2, off2, band, lut)
+        return self._banded_call("sa_score_batch_banded", algo, scoring, s1, off1, s2, off2, band, lut, with_ops=False)
 
     def score_banded_affine_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                                    s2: np.ndarray, off2: np.ndarray, band: int, lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Banded affine score batch (sa_score_batch_banded_affine): the results array (start = -1, nops = 0)."""
-        return self._score_banded_call("sa_score_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut)
-
-    def _score_banded_call(self, fn, algo, scoring, s1, off1, s2, off2, band, lut, extra=(), pre=()):
-        npairs = len(off1) - 1
-        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
-        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
-        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
-        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
-        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
-        lut_p = 0
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
-            lut_p = _ptr(lut)
-        sc = scoring._c()
-        rc = getattr(self.L, fn)(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                 npairs, lut_p, *pre, _band_arg(band), *extra, _ptr(res))
-        self._check(rc, fn)
-        return res[:npairs]
+        return self._banded_call("sa_score_batch_banded_affine", algo, scoring, s1, off1, s2, off2, band, lut, with_ops=False)
 
     def align_banded(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
                      lut: Optional[np.ndarray] = None) -> List[PairResult]:
@@ -686,8 +681,13 @@ class Engine:
     def _align_banded_pairs(self, call, algo, scoring, pairs, band, lut):
         s1, off1, s2, off2 = pack_pairs(pairs)
         res, ops = call(algo, scoring, s1, off1, s2, off2, band, lut)
+        return self._pair_results(res, ops, off1, off2)
+
+    @staticmethod
+    def _pair_results(res, ops, off1, off2) -> List[PairResult]:
+        """An align call's (results, ops) as PairResults: pair p's ops start at off1[p] + off2[p] + p."""
         out = []
-        for p in range(len(pairs)):
+        for p in range(len(res)):
             o = int(off1[p] + off2[p]) + p
             r = res[p]
             out.append(PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]),
@@ -711,57 +711,21 @@ class Engine:
         """Substitution-matrix host-buffer batch (sa_align_batch_matrix): the diagonal term is
         matrix[a, b] (a SubstitutionMatrix or a 256 x 256 int16 table); only the gap terms of
         `scoring` are read; `lut` labels diagonal ops 'M' / 'S'.  Returns (results, ops) as align_packed."""
-        npairs = len(off1) - 1
-        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
-        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
-        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
-        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
-        tab = _submat_arg(matrix)
-        ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
-        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
-        ops = np.zeros(ops_cap, dtype=np.uint8)
-        lut_p = 0
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
-            lut_p = _ptr(lut)
-        sc = scoring._c()
-        rc = self.L.sa_align_batch_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                          npairs, _ptr(tab), lut_p, _ptr(res), _ptr(ops), ops_cap)
-        self._check(rc, "sa_align_batch_matrix")
-        return res[:npairs], ops
+        return self._packed_call("sa_align_batch_matrix", algo, scoring, s1, off1, s2, off2,
+                                 (_submat_arg(matrix), _lut_arg(lut)), True)
 
     def score_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                             s2: np.ndarray, off2: np.ndarray, matrix, lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Substitution-matrix score batch (sa_score_batch_matrix): the results array (start = -1, nops = 0)."""
-        npairs = len(off1) - 1
-        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
-        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
-        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
-        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
-        tab = _submat_arg(matrix)
-        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
-        lut_p = 0
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
-            lut_p = _ptr(lut)
-        sc = scoring._c()
-        rc = self.L.sa_score_batch_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                          npairs, _ptr(tab), lut_p, _ptr(res))
-        self._check(rc, "sa_score_batch_matrix")
-        return res[:npairs]
+        return self._packed_call("sa_score_batch_matrix", algo, scoring, s1, off1, s2, off2,
+                                 (_submat_arg(matrix), _lut_arg(lut)), False)
 
     def align_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
                      lut: Optional[np.ndarray] = None) -> List[PairResult]:
         """align() through the matrix call."""
         s1, off1, s2, off2 = pack_pairs(pairs)
         res, ops = self.align_matrix_packed(algo, scoring, s1, off1, s2, off2, matrix, lut)
-        out = []
-        for p in range(len(pairs)):
-            o = int(off1[p] + off2[p]) + p
-            r = res[p]
-            out.append(PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]),
-                                  int(r["start_j"]), int(r["flags"]), ops[o:o + int(r["nops"])].tobytes()))
-        return out
+        return self._pair_results(res, ops, off1, off2)
 
     def score_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
                      lut: Optional[np.ndarray] = None) -> List[PairResult]:
@@ -776,46 +740,16 @@ class Engine:
         align_banded_packed (SW / NW) or align_banded_affine_packed (LocalGotoh / GlobalGotoh) with the
         diagonal term matrix[a, b]; only the gap terms of `scoring` are read; `lut` labels diagonal ops
         'M' / 'S'.  Returns (results, ops) as align_packed."""
-        npairs = len(off1) - 1
-        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
-        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
-        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
-        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
-        tab = _submat_arg(matrix)
-        ops_cap = int(off1[-1] + off2[-1]) + npairs + 1
-        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
-        ops = np.zeros(ops_cap, dtype=np.uint8)
-        lut_p = 0
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
-            lut_p = _ptr(lut)
-        sc = scoring._c()
-        rc = self.L.sa_align_batch_banded_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                                 npairs, _ptr(tab), lut_p, _band_arg(band), _ptr(res), _ptr(ops), ops_cap)
-        self._check(rc, "sa_align_batch_banded_matrix")
-        return res[:npairs], ops
+        return self._packed_call("sa_align_batch_banded_matrix", algo, scoring, s1, off1, s2, off2,
+                                 (_submat_arg(matrix), _lut_arg(lut), _band_arg(band)), True)
 
     def score_banded_matrix_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                                    s2: np.ndarray, off2: np.ndarray, matrix, band: int,
                                    lut: Optional[np.ndarray] = None) -> np.ndarray:
         """Banded substitution-matrix score batch (sa_score_batch_banded_matrix): the results array
         (start = -1, nops = 0)."""
-        npairs = len(off1) - 1
-        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
-        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
-        off1 = np.ascontiguousarray(off1, dtype=np.uint64)
-        off2 = np.ascontiguousarray(off2, dtype=np.uint64)
-        tab = _submat_arg(matrix)
-        res = np.zeros(max(npairs, 1), dtype=RESULT_DTYPE)
-        lut_p = 0
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(65536)
-            lut_p = _ptr(lut)
-        sc = scoring._c()
-        rc = self.L.sa_score_batch_banded_matrix(self.h, algo, C.byref(sc), _ptr(s1), _ptr(off1), _ptr(s2), _ptr(off2),
-                                                 npairs, _ptr(tab), lut_p, _band_arg(band), _ptr(res))
-        self._check(rc, "sa_score_batch_banded_matrix")
-        return res[:npairs]
+        return self._packed_call("sa_score_batch_banded_matrix", algo, scoring, s1, off1, s2, off2,
+                                 (_submat_arg(matrix), _lut_arg(lut), _band_arg(band)), False)
 
     def align_banded_matrix(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], matrix,
                             band: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
@@ -854,25 +788,13 @@ class Engine:
         match bitmaps.  Expand with expand_ops(algo, a, b, r, blank=...)."""
         off1, off2, bits, bits_off = match_bitmaps(pairs, match)
         res, ops = self.align_bits(algo, scoring, off1, off2, bits, bits_off)
-        out = []
-        for p in range(len(pairs)):
-            o = int(off1[p] + off2[p]) + p
-            r = res[p]
-            out.append(PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]),
-                                  int(r["start_j"]), int(r["flags"]), ops[o:o + int(r["nops"])].tobytes()))
-        return out
+        return self._pair_results(res, ops, off1, off2)
 
     def align(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]],
               lut: Optional[np.ndarray] = None) -> List[PairResult]:
         s1, off1, s2, off2 = pack_pairs(pairs)
         res, ops = self.align_packed(algo, scoring, s1, off1, s2, off2, lut)
-        out = []
-        for p in range(len(pairs)):
-            o = int(off1[p] + off2[p]) + p
-            r = res[p]
-            out.append(PairResult(int(r["score"]), int(r["end_i"]), int(r["end_j"]), int(r["start_i"]),
-                                  int(r["start_j"]), int(r["flags"]), ops[o:o + int(r["nops"])].tobytes()))
-        return out
+        return self._pair_results(res, ops, off1, off2)
 
     def align_device(self, algo: int, scoring: ScoringSystem, d_s1: int, d_off1: int, d_s2: int, d_off2: int,
                      npairs: int, max_m: int, max_n: int, d_res: int, d_ops: int, stream: int = 0,

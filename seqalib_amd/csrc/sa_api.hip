@@ -18,8 +18,7 @@
 #include <thread>
 #include <vector>
 
-#include "sa_dc.h"
-#include "sa_internal.h"
+#include "sa_api_ctx.h"
 
 using namespace sa;
 
@@ -28,94 +27,11 @@ bool dna2_pack(uint8_t* dst, const uint8_t* src, uint64_t n);
 void ops2_unpack(uint8_t* dst, const uint8_t* src, uint32_t n, const uint32_t* lut);
 }  // namespace sa
 
-constexpr int kKEv = 6;   // SEQALIB_KERNEL_TIMING events per fill launch (two per variant, <= 3)
-// Cross-call pipeline: workspace slots (call k's fill waits for call k-2's traceback).  Three slots
-// with the fills alternating between two streams (call k+1's fill starting in call k's fill tail)
-// measured slower, 19.5 vs 18.2 ms per headline step (round 5, profiles/pipe_slots_ab_r05.txt).
-constexpr int kPipeSlots = SA_PIPELINE_DEPTH;
-
-struct sa_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    // cached device workspace (direction slots + row buffers + LUT bits)
-    uint8_t* ws = nullptr;
-    uint64_t ws_bytes = 0;
-    uint64_t ws_limit = 0;  // 0 = automatic
-    // cached device I/O buffers for the host API
-    uint8_t* io = nullptr;
-    uint64_t io_bytes = 0;
-    // timing of the last call
-    std::vector<hipEvent_t> events;  // 3 per fill launch: start, fill end, traceback end
-    int launches = 0;
-    // $SEQALIB_KERNEL_TIMING: per launch and variant, events around the fill kernel alone
-    // (kKEv per launch: [2k] before, [2k + 1] after variant k's fill; kvars[launch] variants)
-    std::vector<hipEvent_t> kevents;
-    std::vector<int> kvars;
-    hipStream_t timed_stream = nullptr;
-    // aux words of the T16 decision (sa_internal.h kAux*), one kAuxWords slot per pipeline slot
-    uint32_t* aux = nullptr;
-    // plan of the last call: one entry per kernel variant it enqueued (T16 first when the batch
-    // was T16-eligible by scoring and shape; the device picked one by the batch alphabet, and
-    // h_sel receives that choice asynchronously, ev_sel marks its arrival)
-    int nvar = 0, var_kernel[2] = {0, 0}, var_R[2] = {0, 0}, var_W[2] = {0, 0}, var_records[2] = {0, 0};
-    uint32_t* h_sel = nullptr;
-    hipEvent_t ev_sel = nullptr;
-    // the last call's selection when the host decided it (host_alphabet), else -1: then the
-    // device's word arrives in h_sel (a host write there could race with a pending download)
-    int host_sel = -1;
-    // cross-call pipeline of the device API (sa_set_pipeline): fills on s_fill, tracebacks on
-    // s_tb, kPipeSlots workspace slots; ev_slot[k] = traceback of the last call that used slot k done
-    int pipeline = 0;
-    // Band-unit hand-off buffer (score-only SW / NW fills, sa_fill_impl.h BU): the row granules, the
-    // column-segment state and the per-unit maxima, all {tag, value} words polled by their consumers.
-    // Only those fills write it (every kernel that touches it runs on the fill stream, so one copy
-    // serves both pipeline slots), and it is zeroed when allocated and whenever hand_tag wraps: a word
-    // there carries the tag of the launch that wrote it or 0, so a consumer can never take an earlier
-    // launch's word -- of any shape -- for its producer's.  hand_tag: the last launch's tag, 1..65535.
-    uint8_t* hand = nullptr;
-    uint64_t hand_bytes = 0;
-    uint32_t hand_tag = 0;
-    bool hand_dirty = false;   // (tests: sa_test_hook poisoned it) zero before the next launch
-    hipStream_t s_fill = nullptr, s_tb = nullptr;
-    hipEvent_t ev_in = nullptr, ev_slot[kPipeSlots] = {};
-    // The f16 SW cell (sa_fill_so2.hip FK) re-runs in int32 every pair whose score may pass 2,000.
-    // Each of its launches has a number f16_seq; its end cell posts {seq, flagged pairs} to h_f16
-    // (coherent pinned, d_f16 on the device) and f16_cnt[seq % 4] keeps the launch's pair count.
-    // A launch that flagged more than 1/64 of its pairs turns the cell off for the context
-    // (f16_off): such batches run the 16-bit integer cell, exact to 8,191, instead of re-running.
-    unsigned long long* h_f16 = nullptr;
-    unsigned long long* d_f16 = nullptr;
-    uint32_t f16_seq = 0, f16_seen = 0, f16_cnt[4] = {};
-    bool f16_off = false;
-    uint64_t pipe_k = 0;
-    // SPLIT plans (few pairs, one workgroup per band): [ticket, pad to 256 B][granules][partials]
-    uint8_t* split = nullptr;
-    uint64_t split_bytes = 0;
-    // HirschbergSA / MyersMillerSA level-loop buffers and the host API's pinned upload staging
-    sa::DcWork dc;
-    sa::HostBuf<uint8_t> stage, ostage;
-    // the small-call path (align_tiny): coherent pinned inputs and outputs the kernel reads and
-    // writes in place (host pointer, device pointer)
-    uint8_t* tiny_io = nullptr;
-    uint8_t* tiny_dev = nullptr;
-    // host API: download stream and per-chunk events (align_host)
-    hipStream_t s_out = nullptr;
-    std::vector<hipEvent_t> host_ev;
-    // Calls on one context are ordered: every call's stream waits for ev_last, the end of the
-    // last un-pipelined call (whatever stream it ran on), since they share the workspace, the
-    // I/O cache and the DC buffers.
-    hipEvent_t ev_last = nullptr;
-    bool ev_last_set = false;
-    // kernels the last call launched after its fills' end (ev[1]): walks, the segmented traceback,
-    // the SPLIT fallback behind them.  A score call launches none, and sa_last_timings then reports
-    // traceback_ms = 0 instead of the few microseconds between two event records
-    int tb_kernels = 0;
-};
-
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
+
+namespace sa {   // (sa_api_ctx.h: shared with sa_api_banded.hip)
 
 int fail(sa_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -126,12 +42,6 @@ int fail(sa_ctx* c, int code, const std::string& msg) {
 int hip_fail(sa_ctx* c, hipError_t e, const char* what) {
     return fail(c, SA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-
-#define SA_HIP(c, call)                                   \
-    do {                                                  \
-        hipError_t e_ = (call);                           \
-        if (e_ != hipSuccess) return hip_fail(c, e_, #call); \
-    } while (0)
 
 // Order a call on stream st after the context's last call, and mark the end of this one.
 int order_after_last(sa_ctx* c, hipStream_t st) {
@@ -145,7 +55,7 @@ int mark_last(sa_ctx* c, hipStream_t st) {
     return SA_OK;
 }
 // Before a context buffer is freed: every stream that may still use it has finished.
-int drain(sa_ctx* c) {
+static int drain(sa_ctx* c) {   // (this unit's alone)
     SA_HIP(c, hipStreamSynchronize(c->stream));
     if (c->s_fill) SA_HIP(c, hipStreamSynchronize(c->s_fill));
     if (c->s_tb) SA_HIP(c, hipStreamSynchronize(c->s_tb));
@@ -153,6 +63,58 @@ int drain(sa_ctx* c) {
     if (c->ev_last_set) SA_HIP(c, hipEventSynchronize(c->ev_last));
     return SA_OK;
 }
+
+int ensure_ws(sa_ctx* c, uint64_t need) {
+    if (c->ws_bytes >= need) return SA_OK;
+    if (c->ws) {
+        if (int rc = drain(c)) return rc;
+        (void)hipFree(c->ws);
+        c->ws = nullptr;
+        c->ws_bytes = 0;
+    }
+    hipError_t e = hipMalloc(&c->ws, need);
+    if (e != hipSuccess) {
+        c->ws = nullptr;
+        return fail(c, SA_ERR_NOMEM, "hipMalloc workspace of " + std::to_string(need) + " bytes failed");
+    }
+    c->ws_bytes = need;
+    return SA_OK;
+}
+
+// The I/O cache of the host API (device copies of the caller's buffers; the device API keeps the
+// LUT bits in its tail): grow-only.
+int ensure_io(sa_ctx* c, uint64_t need) {
+    if (c->io_bytes >= need) return SA_OK;
+    if (c->io) {
+        if (int rc = drain(c)) return rc;
+        (void)hipFree(c->io);
+        c->io = nullptr;
+        c->io_bytes = 0;
+    }
+    if (hipMalloc(&c->io, need) != hipSuccess) {
+        c->io = nullptr;
+        return fail(c, SA_ERR_NOMEM, "hipMalloc of I/O buffers (" + std::to_string(need) + " bytes) failed");
+    }
+    c->io_bytes = need;
+    return SA_OK;
+}
+
+uint64_t ws_budget(sa_ctx* c) {
+    if (c->ws_limit) return c->ws_limit;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 1ull << 30;
+    return (uint64_t)((fr + c->ws_bytes) * 0.8);
+}
+
+bool lut_is_identity(const uint8_t* lut) {
+    for (int a = 0; a < 256; ++a)
+        for (int b = 0; b < 256; ++b)
+            if ((lut[a * 256 + b] != 0) != (a == b)) return false;
+    return true;
+}
+}  // namespace sa
+
+namespace {
 
 // ------------------------------------------------------------------------------- planning
 struct Plan {
@@ -477,48 +439,6 @@ int zero_hand(sa_ctx* c, uint64_t need, hipStream_t st, bool grow) {
     c->hand_tag = 0;
     c->hand_dirty = false;
     return SA_OK;
-}
-
-int ensure_ws(sa_ctx* c, uint64_t need) {
-    if (c->ws_bytes >= need) return SA_OK;
-    if (c->ws) {
-        if (int rc = drain(c)) return rc;
-        (void)hipFree(c->ws);
-        c->ws = nullptr;
-        c->ws_bytes = 0;
-    }
-    hipError_t e = hipMalloc(&c->ws, need);
-    if (e != hipSuccess) {
-        c->ws = nullptr;
-        return fail(c, SA_ERR_NOMEM, "hipMalloc workspace of " + std::to_string(need) + " bytes failed");
-    }
-    c->ws_bytes = need;
-    return SA_OK;
-}
-
-// The I/O cache of the host API (device copies of the caller's buffers; the device API keeps the
-// LUT bits in its tail): grow-only.
-int ensure_io(sa_ctx* c, uint64_t need) {
-    if (c->io_bytes >= need) return SA_OK;
-    if (c->io) {
-        if (int rc = drain(c)) return rc;
-        (void)hipFree(c->io);
-        c->io = nullptr;
-        c->io_bytes = 0;
-    }
-    if (hipMalloc(&c->io, need) != hipSuccess) {
-        c->io = nullptr;
-        return fail(c, SA_ERR_NOMEM, "hipMalloc of I/O buffers (" + std::to_string(need) + " bytes) failed");
-    }
-    c->io_bytes = need;
-    return SA_OK;
-}
-
-uint64_t ws_budget(sa_ctx* c) {
-    if (c->ws_limit) return c->ws_limit;
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 1ull << 30;
-    return (uint64_t)((fr + c->ws_bytes) * 0.8);
 }
 
 // 16-bit (score, column) keys for the running maximum are exact when every local score and
@@ -1319,13 +1239,6 @@ int run_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* d1, con
     return SA_OK;
 }
 
-bool lut_is_identity(const uint8_t* lut) {
-    for (int a = 0; a < 256; ++a)
-        for (int b = 0; b < 256; ++b)
-            if ((lut[a * 256 + b] != 0) != (a == b)) return false;
-    return true;
-}
-
 // the match table is equality on every symbol pair these sequences hold (seq1 symbol x seq2 symbol):
 // a caller's table for equal<char> then needs no upload (the kernels compare bytes)
 bool lut_identity_on(const uint8_t* lut, const uint8_t* s1, uint64_t t1, const uint8_t* s2, uint64_t t2) {
@@ -1500,6 +1413,8 @@ void par_copy(void* dst, const void* src, uint64_t n) {
     copy_pool()->copy(dst, src, n);
 }
 
+}  // namespace
+namespace sa {   // (sa_api_ctx.h)
 // fn(a, b) over items [0, n) in slices of `grain` items, on the copy pool's workers and this thread
 void par_for(uint64_t n, uint64_t grain, std::function<void(uint64_t, uint64_t)> fn) {
     if (n <= grain) {
@@ -1508,6 +1423,8 @@ void par_for(uint64_t n, uint64_t grain, std::function<void(uint64_t, uint64_t)>
     }
     copy_pool()->copy(nullptr, nullptr, n, grain, std::move(fn));
 }
+}  // namespace sa
+namespace {
 
 // Host API batches may be cut into contiguous pair ranges ("chunks") of near-equal cells run
 // through the cross-call pipeline, so chunk g+1's upload and chunk g-1's download overlap chunk
@@ -2339,548 +2256,6 @@ int sa_score_batch_device(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
     return device_batch(c, algo, sc, d1, o1, d2, o2, npairs, max_m, max_n, d_lut, d_res, nullptr, stream, true);
 }
 
-// ------------------------------------------------------------------------- banded calls
-// sa_align_batch_banded / sa_score_batch_banded (kernels: sa_banded.hip).  Every pair gets the fill
-// variant (cells per lane R, lanes per pair L) its clipped band fits; the pairs of one variant are
-// launched together, longest first, in as many launches as sa_set_workspace_limit leaves room for
-// their records.  A score call stores no records and launches no walk.
-// sa_align_batch_banded_affine / sa_score_batch_banded_affine (kernels: sa_banded_affine.hip) run the
-// same batching with their own checks, the first kBandAffineVariants variants and 4-bit records.
-// sa_align_batch_banded_matrix / sa_score_batch_banded_matrix (banded_matrix_batch, below the matrix
-// calls) run it too, linear or affine by algorithm, on recoded sequences with the kMatchSub fills.
-// sa_align_batch_banded_ends_free / sa_score_batch_banded_ends_free (banded_ends_free_batch) run it with
-// the ends-free fills and walks (sa_banded_free.hip, sa_banded_affine_free.hip).
-
-// Algorithm, scoring and band checks shared with sa_banded_plan_query (c may be NULL).
-static int banded_prologue(sa_ctx* c, int* algo, const sa_scoring* sc, uint32_t band) {
-    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
-    if (*algo < SA_SW || *algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
-    if (*algo == SA_LOCAL_GOTOH || *algo == SA_GLOBAL_GOTOH || *algo == SA_MYERS_MILLER)
-        return fail(c, SA_ERR_UNSUPPORTED, "banded calls support the linear-gap algorithms only (SA_SW, SA_NW, SA_HIRSCHBERG)");
-    if (*algo == SA_HIRSCHBERG) *algo = SA_NW;
-    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: |n - m| + 2 * band + 1 diagonals overflow 32 bits");
-    if (band == 0 && !sc->allow_mismatch)
-        return fail(c, SA_ERR_UNSUPPORTED, "band = 0 needs allow_mismatch (a one-diagonal band has no other candidate)");
-    return SA_OK;
-}
-
-// The same for sa_align_batch_banded_affine / sa_score_batch_banded_affine / sa_banded_affine_plan_query.
-static int banded_affine_prologue(sa_ctx* c, int algo, const sa_scoring* sc, uint32_t band) {
-    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
-    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
-    if (algo != SA_LOCAL_GOTOH && algo != SA_GLOBAL_GOTOH)
-        return fail(c, SA_ERR_UNSUPPORTED, "banded affine calls support SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH only");
-    if (sc->gap_extend > 0)
-        return fail(c, SA_ERR_UNSUPPORTED, "banded affine calls need gap_extend <= 0 (the records decide the walk only then)");
-    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: |n - m| + 2 * band + 1 diagonals overflow 32 bits");
-    if (band == 0 && !sc->allow_mismatch)
-        return fail(c, SA_ERR_UNSUPPORTED, "band = 0 needs allow_mismatch (a one-diagonal band has no other candidate)");
-    return SA_OK;
-}
-
-// The seeded calls' band of one pair (seed NULL: the corridor band of every other call).
-struct BandSeed {
-    int32_t diag;        // the seed diagonal, -m <= diag <= n (checked by the caller)
-    uint32_t free_ends;
-    uint64_t pair;       // for the message
-};
-
-// The seeded legality rule: the band must hold a legal begin and a legal end (include/seqalib_hip.h).
-static int banded_seed_legal(sa_ctx* c, const BandSeed& sd, const BandGeom& g, int64_t m, int64_t n) {
-    const bool begin = (g.lo <= 0 && 0 <= g.hi) || ((sd.free_ends & kFreeSeq2Begin) && g.hi >= 0) ||
-                       ((sd.free_ends & kFreeSeq1Begin) && g.lo <= 0);
-    const int64_t d = n - m;
-    const bool end = (g.lo <= d && d <= g.hi) || ((sd.free_ends & kFreeSeq2End) && g.lo <= d) ||
-                     ((sd.free_ends & kFreeSeq1End) && g.hi >= d);
-    if (begin && end) return SA_OK;
-    return fail(c, SA_ERR_UNSUPPORTED,
-                "pair " + std::to_string(sd.pair) + ": the band [" + std::to_string(g.lo) + ", " + std::to_string(g.hi) +
-                    "] holds no legal " + (begin ? "end" : end ? "begin" : "begin and no legal end") +
-                    " under free_ends = " + std::to_string(sd.free_ends));
-}
-
-// One pair's geometry and fill variant, or why the banded path does not take it.
-static int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t m, uint64_t n, uint32_t band,
-                            BandGeom* g, int* variant, const BandSeed* seed = nullptr) {
-    if (m >= (1u << 24) || n >= (1u << 24)) return fail(c, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
-    auto a = [](int32_t x) { return (int64_t)(x < 0 ? -(int64_t)x : x); };
-    auto geom = [&]() {
-        const int32_t w = (int32_t)std::min(band, kBandMaxW);
-        return seed ? band_geom_seeded((int32_t)m, (int32_t)n, w, seed->diag) : band_geom((int32_t)m, (int32_t)n, w);
-    };
-    if (algo == SA_LOCAL_GOTOH || algo == SA_GLOBAL_GOTOH) {   // (the linear calls never get here with these)
-        const int64_t big = std::max(std::max(a(sc->gap_open) + a(sc->gap_extend), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
-        if ((int64_t)(m + n + 1) * big + 10000 >= kBandScoreLimit)
-            return fail(c, SA_ERR_UNSUPPORTED,
-                        "banded affine calls need (m + n + 1) * max(|gap_open| + |gap_extend|, |match|, |mismatch|) + 10000 < 2^29");
-        *g = geom();
-        *variant = band_affine_variant(g->beff);
-        if (*variant < 0)
-            return fail(c, SA_ERR_UNSUPPORTED, "band of " + std::to_string(g->beff) + " diagonals inside the matrix exceeds the " +
-                                                   std::to_string(kBandAffineMaxDiagonals) + " one wave holds with three values per cell");
-        if (algo == SA_LOCAL_GOTOH && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
-            return fail(c, SA_ERR_UNSUPPORTED, "banded LocalGotoh needs (m + 1) * band diagonals < 2^31");
-        return seed ? banded_seed_legal(c, *seed, *g, (int64_t)m, (int64_t)n) : SA_OK;
-    }
-    const int64_t big = std::max(std::max(a(sc->gap), a(sc->match)), sc->allow_mismatch ? a(sc->mismatch) : 0);
-    if ((int64_t)(m + n + 1) * big >= kBandScoreLimit)
-        return fail(c, SA_ERR_UNSUPPORTED, "banded calls need (m + n + 1) * max(|gap|, |match|, |mismatch|) < 2^29");
-    *g = geom();
-    *variant = band_variant(g->beff);
-    if (*variant < 0)
-        return fail(c, SA_ERR_UNSUPPORTED, "band of " + std::to_string(g->beff) + " diagonals inside the matrix exceeds the " +
-                                               std::to_string(kBandMaxDiagonals) + " one wave holds");
-    if (algo == SA_SW && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
-        return fail(c, SA_ERR_UNSUPPORTED, "banded SW needs (m + 1) * band diagonals < 2^31");
-    return seed ? banded_seed_legal(c, *seed, *g, (int64_t)m, (int64_t)n) : SA_OK;
-}
-
-// A matrix band call's recode (banded_matrix_batch): the batch's K used symbols in byte order, their
-// codes, and the used K x K corner of the caller's table, dense (row stride K; K >= 1).
-struct BandSub {
-    uint8_t code[256];
-    int syms[kSubMaxSyms];
-    int K;
-    std::vector<int16_t> tab;   // kSubMaxSyms^2 entries, the first K * K used
-};
-
-// sub (the matrix band calls): the caller has run the algorithm, scoring and buffer checks, *sc holds
-// the table's extremes as match / mismatch with allow_mismatch = 1 (what banded_pair_plan bounds the
-// scores by), lut only labels, and the sequences are recoded on their way to the device.
-// free_ends >= 0 (the ends-free calls, algo SA_NW / SA_HIRSCHBERG or SA_GLOBAL_GOTOH): the SA_FREE_* bits
-// for the ends-free fills and walks; every check, the grouping and the launches are the global call's.
-// diag (the seeded calls, with free_ends >= 0; the caller has checked -m <= diag[p] <= n): every pair's
-// band lies round its seed diagonal, and the seeded fills and walks (sa_banded_seeded.hip,
-// sa_banded_affine_seeded.hip) read the diagonals from behind each launch's idx entries.
-static int banded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                        const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                        sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb, bool affine = false,
-                        const BandSub* sub = nullptr, int free_ends = -1, const int32_t* diag = nullptr) {
-    // (the checks that need no context come first, so they answer without a device too)
-    int rc = sub ? SA_OK : affine ? banded_affine_prologue(c, algo, sc, band) : banded_prologue(c, &algo, sc, band);
-    if (rc) return rc;
-    const bool ends_free = free_ends >= 0;
-    auto pair_plan = [&](uint32_t p, BandGeom* g, int* v) {
-        const BandSeed sd{diag ? diag[p] : 0, (uint32_t)(ends_free ? free_ends : 0), p};
-        return banded_pair_plan(c, algo, sc, off1[p + 1] - off1[p], off2[p + 1] - off2[p], band, g, v, diag ? &sd : nullptr);
-    };
-    const int nvariants = affine ? kBandAffineVariants : kBandVariants;
-    auto rec_words = [&](const BandGeom& g, int v) { return affine ? band_affine_rec_words(g, v) : band_rec_words(g, v); };
-    if ((affine || sub || ends_free) && off1 && off2) {   // the affine, matrix and ends-free calls' per-pair limits answer without a context as well
-        for (uint32_t p = 0; p < npairs; ++p) {
-            if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
-            BandGeom g;
-            int v = 0;
-            if ((rc = pair_plan(p, &g, &v))) return rc;
-        }
-    }
-    if (!c) return fail(nullptr, SA_ERR_ARG, "ctx is NULL");
-    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
-    if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
-    if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
-    for (uint32_t p = 0; p < npairs; ++p)
-        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
-    const uint64_t t1 = off1[npairs], t2 = off2[npairs];
-    const uint64_t ops_total = notb ? 0 : t1 + t2 + npairs;
-    if (ops_cap < ops_total) return fail(c, SA_ERR_CAPACITY, "ops buffer needs " + std::to_string(ops_total) + " bytes");
-    if (!npairs) return SA_OK;
-    SA_HIP(c, hipSetDevice(c->device));
-    if ((rc = order_after_last(c, c->stream))) return rc;
-    const uint32_t w = std::min(band, kBandMaxW);
-
-    // pairs by variant, longest first; record offsets restart at every launch
-    std::vector<uint64_t> words(npairs);
-    std::vector<uint32_t> bucket[kBandVariants];
-    for (uint32_t p = 0; p < npairs; ++p) {
-        BandGeom g;
-        int v = 0;
-        if ((rc = pair_plan(p, &g, &v))) return rc;
-        words[p] = notb ? 0 : rec_words(g, v);
-        bucket[v].push_back(p);
-    }
-    // A launch of fewer waves than the device has SIMDs runs as long as one wave does, so two such
-    // launches in a row cost two of those where one launch of both costs one.  The pairs of a variant
-    // therefore join the NEXT variant (one step in (R, L): twice the diagonals, at most twice the
-    // records) when that variant is in use too, the joint launch still has at most a wave per SIMD,
-    // and every moved pair's records still fit the workspace budget; a pair moves at most one step
-    // (a variant that took pairs in stays where it is).  So a pair's records stay within twice what
-    // sa_banded_plan_query reports, and a call that fits the limit unmerged never fails merged.
-    // $SEQALIB_BAND_MERGE=0: every pair keeps the narrowest variant that holds it (tests).
-    const uint64_t budget_words = notb ? 0 : ws_budget(c) / 4;
-    const char* merge_env = getenv("SEQALIB_BAND_MERGE");
-    if (!(merge_env && merge_env[0] == '0')) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
-        const uint64_t simds = 4ull * (uint64_t)cus;
-        bool took_in = false;   // bucket[v] holds pairs moved up from v - 1
-        for (int v = 0; v + 1 < nvariants; ++v) {
-            const bool fixed = took_in;
-            took_in = false;
-            if (fixed || bucket[v].empty() || bucket[v + 1].empty()) continue;
-            const uint64_t ppw = (uint64_t)(kWave / kBandL[v + 1]);
-            if ((bucket[v].size() + bucket[v + 1].size() + ppw - 1) / ppw > simds) continue;
-            std::vector<uint64_t> moved(bucket[v].size(), 0);
-            bool fits = true;
-            for (size_t k = 0; k < bucket[v].size() && !notb && fits; ++k) {
-                const uint32_t p = bucket[v][k];
-                const int32_t pm = (int32_t)(off1[p + 1] - off1[p]), pn = (int32_t)(off2[p + 1] - off2[p]);
-                const BandGeom g = diag ? band_geom_seeded(pm, pn, (int32_t)w, diag[p]) : band_geom(pm, pn, (int32_t)w);
-                moved[k] = rec_words(g, v + 1);
-                fits = moved[k] <= budget_words;
-            }
-            if (!fits) continue;
-            for (size_t k = 0; k < bucket[v].size(); ++k) {
-                words[bucket[v][k]] = moved[k];
-                bucket[v + 1].push_back(bucket[v][k]);
-            }
-            bucket[v].clear();
-            took_in = true;
-        }
-    }
-    struct Launch { int v; uint32_t first, count; };
-    std::vector<Launch> launches;
-    std::vector<uint32_t> idx;
-    std::vector<uint64_t> recoff;
-    idx.reserve(npairs);
-    recoff.reserve(npairs);
-    uint64_t ws_words = 0;
-    int top_v = 0;
-    for (int v = 0; v < nvariants; ++v) {
-        std::vector<uint32_t>& b = bucket[v];
-        if (b.empty()) continue;
-        top_v = v;
-        std::stable_sort(b.begin(), b.end(), [&](uint32_t x, uint32_t y) {
-            return off1[x + 1] - off1[x] + off2[x + 1] - off2[x] > off1[y + 1] - off1[y] + off2[y + 1] - off2[y];
-        });
-        Launch cur{v, (uint32_t)idx.size(), 0};
-        uint64_t used = 0;
-        for (uint32_t p : b) {
-            if (!notb && words[p] > budget_words)
-                return fail(c, SA_ERR_NOMEM, "the band records of one pair (" + std::to_string(words[p] * 4) +
-                                                 " bytes) exceed the workspace limit");
-            if (cur.count && used + words[p] > budget_words) {
-                launches.push_back(cur);
-                cur = Launch{v, (uint32_t)idx.size(), 0};
-                used = 0;
-            }
-            idx.push_back(p);
-            recoff.push_back(used);
-            used += words[p];
-            cur.count++;
-            ws_words = std::max(ws_words, used);
-        }
-        launches.push_back(cur);
-    }
-    if (!notb && (rc = ensure_ws(c, std::max<uint64_t>(ws_words * 4, 256)))) return rc;
-    // seeded: each launch's block of the uploaded array is [its idx entries][their diagonals]
-    const uint32_t idx_stride = diag ? 2 : 1;
-    if (diag) {
-        std::vector<uint32_t> both;
-        both.reserve(2ull * npairs);
-        for (const Launch& ln : launches) {
-            both.insert(both.end(), idx.begin() + ln.first, idx.begin() + ln.first + ln.count);
-            for (uint32_t k = 0; k < ln.count; ++k) both.push_back((uint32_t)diag[idx[ln.first + k]]);
-        }
-        idx.swap(both);
-    }
-
-    const bool use_lut = lut && !lut_is_identity(lut);
-    std::vector<uint32_t> bits;
-    if (use_lut) {
-        bits.assign(2048, 0);
-        if (sub) {   // the walk reads codes: the label table over codes (equality of codes is equality of bytes)
-            for (int a = 0; a < sub->K; ++a)
-                for (int b = 0; b < sub->K; ++b)
-                    if (lut[sub->syms[a] * 256 + sub->syms[b]]) bits[a * 8 + b / 32] |= 1u << (b % 32);
-        } else {
-            for (int a = 0; a < 256; ++a)
-                for (int b = 0; b < 256; ++b)
-                    if (lut[a * 256 + b]) bits[a * 8 + b / 32] |= 1u << (b % 32);
-        }
-    }
-    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t b_s1 = al(t1 + 1), b_s2 = al(t2 + 1), b_o = al(8ull * (npairs + 1)), b_res = al(sizeof(sa_result) * (uint64_t)npairs);
-    const uint64_t b_ops = al(ops_total + 1), b_bits = al(8192), b_idx = al(4ull * idx.size()), b_ro = al(8ull * npairs);
-    const uint64_t b_tab = sub ? al(2ull * kSubMaxSyms * kSubMaxSyms) : 0;
-    if ((rc = ensure_io(c, b_s1 + b_s2 + 2 * b_o + b_res + b_ops + b_bits + b_idx + b_ro + b_tab))) return rc;
-    uint8_t* q = c->io;
-    uint8_t* const d1 = q; q += b_s1;
-    uint8_t* const d2 = q; q += b_s2;
-    uint64_t* const do1 = reinterpret_cast<uint64_t*>(q); q += b_o;
-    uint64_t* const do2 = reinterpret_cast<uint64_t*>(q); q += b_o;
-    sa_result* const dres = reinterpret_cast<sa_result*>(q); q += b_res;
-    uint8_t* const dops = q; q += b_ops;
-    uint32_t* const dbits = reinterpret_cast<uint32_t*>(q); q += b_bits;
-    uint32_t* const didx = reinterpret_cast<uint32_t*>(q); q += b_idx;
-    uint64_t* const dro = reinterpret_cast<uint64_t*>(q); q += b_ro;
-    int16_t* const dtab = reinterpret_cast<int16_t*>(q);
-    hipStream_t st = c->stream;
-    if (sub) {   // pinned staging: [Seq1 codes][Seq2 codes][table]
-        SA_HIP(c, c->stage.alloc(b_s1 + b_s2 + b_tab));
-        uint8_t* const h1 = c->stage.data();
-        uint8_t* const h2 = h1 + b_s1;
-        const uint8_t* const code = sub->code;
-        par_for(t1, 1u << 20, [&](uint64_t lo, uint64_t hi) { for (uint64_t k = lo; k < hi; ++k) h1[k] = code[seq1[k]]; });
-        par_for(t2, 1u << 20, [&](uint64_t lo, uint64_t hi) { for (uint64_t k = lo; k < hi; ++k) h2[k] = code[seq2[k]]; });
-        memcpy(h2 + b_s2, sub->tab.data(), 2ull * kSubMaxSyms * kSubMaxSyms);
-        if (t1) SA_HIP(c, hipMemcpyAsync(d1, h1, t1, hipMemcpyHostToDevice, st));
-        if (t2) SA_HIP(c, hipMemcpyAsync(d2, h2, t2, hipMemcpyHostToDevice, st));
-        SA_HIP(c, hipMemcpyAsync(dtab, h2 + b_s2, 2ull * kSubMaxSyms * kSubMaxSyms, hipMemcpyHostToDevice, st));
-    } else {
-        if (t1) SA_HIP(c, hipMemcpyAsync(d1, seq1, t1, hipMemcpyHostToDevice, st));
-        if (t2) SA_HIP(c, hipMemcpyAsync(d2, seq2, t2, hipMemcpyHostToDevice, st));
-    }
-    SA_HIP(c, hipMemcpyAsync(do1, off1, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
-    SA_HIP(c, hipMemcpyAsync(do2, off2, 8ull * (npairs + 1), hipMemcpyHostToDevice, st));
-    if (use_lut) SA_HIP(c, hipMemcpyAsync(dbits, bits.data(), 8192, hipMemcpyHostToDevice, st));
-    SA_HIP(c, hipMemcpyAsync(didx, idx.data(), 4ull * idx.size(), hipMemcpyHostToDevice, st));
-    SA_HIP(c, hipMemcpyAsync(dro, recoff.data(), 8ull * npairs, hipMemcpyHostToDevice, st));
-
-    const bool kernel_timing = getenv("SEQALIB_KERNEL_TIMING") != nullptr;
-    c->launches = 0;
-    c->kvars.clear();
-    c->timed_stream = st;
-    c->tb_kernels = 0;
-    const int mm = sub ? kMatchSub : use_lut ? kMatchLut : kMatchEq;
-    for (const Launch& ln : launches) {
-        while ((int)c->events.size() < 3 * (c->launches + 1)) {
-            hipEvent_t ev;
-            SA_HIP(c, hipEventCreate(&ev));
-            c->events.push_back(ev);
-        }
-        hipEvent_t* ev = &c->events[3 * c->launches];
-        hipEvent_t* kev = nullptr;
-        if (kernel_timing) {
-            while ((int)c->kevents.size() < kKEv * (c->launches + 1)) {
-                hipEvent_t e;
-                SA_HIP(c, hipEventCreate(&e));
-                c->kevents.push_back(e);
-            }
-            c->kvars.resize(c->launches + 1);
-            c->kvars[c->launches] = 1;
-            kev = &c->kevents[kKEv * c->launches];
-        }
-        BandParams bp;
-        bp.seq1 = d1;
-        bp.off1 = do1;
-        bp.seq2 = d2;
-        bp.off2 = do2;
-        bp.lutbits = use_lut ? dbits : nullptr;
-        bp.idx = didx + (uint64_t)idx_stride * ln.first;
-        bp.recoff = dro + ln.first;
-        bp.rec = reinterpret_cast<uint32_t*>(c->ws);
-        bp.res = dres;
-        bp.ops = dops;
-        bp.count = ln.count;
-        bp.band = w;
-        bp.gap = sc->gap;
-        bp.match = sc->match;
-        bp.mismatch = sc->allow_mismatch ? sc->mismatch : kBandNeg;
-        bp.allow = sc->allow_mismatch;
-        bp.R = kBandR[ln.v];
-        bp.L = kBandL[ln.v];
-        bp.submat = sub ? dtab : nullptr;
-        bp.sub_k = sub ? (uint32_t)sub->K : 0;
-        bp.free_ends = ends_free ? (uint32_t)free_ends : 0;
-        BandAffineParams ap;
-        static_cast<BandParams&>(ap) = bp;
-        ap.gap_open = sc->gap_open;
-        ap.gap_extend = sc->gap_extend;
-        SA_HIP(c, hipEventRecord(ev[0], st));
-        if (kev) SA_HIP(c, hipEventRecord(kev[0], st));
-        if (diag && affine) SA_HIP(c, launch_banded_affine_seeded_fill(ln.v, use_lut, !notb, ap, st));
-        else if (diag) SA_HIP(c, launch_banded_seeded_fill(ln.v, use_lut, !notb, bp, st));
-        else if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_fill(ln.v, use_lut, !notb, ap, st));
-        else if (ends_free) SA_HIP(c, launch_banded_free_fill(ln.v, use_lut, !notb, bp, st));
-        else if (affine) SA_HIP(c, launch_banded_affine_fill(algo, ln.v, mm, !notb, ap, st));
-        else SA_HIP(c, launch_banded_fill(algo, ln.v, mm, !notb, bp, st));
-        if (kev) SA_HIP(c, hipEventRecord(kev[1], st));
-        SA_HIP(c, hipEventRecord(ev[1], st));
-        if (!notb) {
-            if (diag && affine) SA_HIP(c, launch_banded_affine_seeded_tb(use_lut, ap, st));
-            else if (diag) SA_HIP(c, launch_banded_seeded_tb(use_lut, bp, st));
-            else if (ends_free && affine) SA_HIP(c, launch_banded_affine_free_tb(use_lut, ap, st));
-            else if (ends_free) SA_HIP(c, launch_banded_free_tb(use_lut, bp, st));
-            else if (affine) SA_HIP(c, launch_banded_affine_tb(algo, use_lut, ap, st));
-            else SA_HIP(c, launch_banded_tb(algo, use_lut, bp, st));
-            c->tb_kernels++;
-        }
-        SA_HIP(c, hipEventRecord(ev[2], st));
-        c->launches++;
-    }
-    c->nvar = 1;
-    c->host_sel = -1;
-    c->var_kernel[0] = SA_KERNEL_BANDED;
-    c->var_R[0] = kBandR[top_v];
-    c->var_W[0] = 1;
-    c->var_records[0] = notb ? SA_RECORDS_NONE : affine ? SA_RECORDS_BAND4 : SA_RECORDS_BAND2;
-
-    // outputs through the context's pinned staging, as the other host paths: [results][ops]
-    SA_HIP(c, c->ostage.alloc(b_res + ops_total));
-    sa_result* const sres = reinterpret_cast<sa_result*>(c->ostage.data());
-    uint8_t* const sops = c->ostage.data() + b_res;
-    SA_HIP(c, hipMemcpyAsync(sres, dres, sizeof(sa_result) * (uint64_t)npairs, hipMemcpyDeviceToHost, st));
-    if (!notb && ops_total) SA_HIP(c, hipMemcpyAsync(sops, dops, ops_total, hipMemcpyDeviceToHost, st));
-    if ((rc = mark_last(c, st))) return rc;
-    SA_HIP(c, hipStreamSynchronize(st));
-    memcpy(results, sres, sizeof(sa_result) * (uint64_t)npairs);
-    for (uint32_t p = 0; p < npairs && !notb; ++p) {
-        const uint64_t o = off1[p] + off2[p] + p;
-        memcpy(ops + o, sops + o, results[p].nops);
-    }
-    return SA_OK;
-}
-
-int sa_align_batch_banded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                          const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                          sa_result* results, uint8_t* ops, uint64_t ops_cap) {
-    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, false);
-}
-
-int sa_score_batch_banded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                          const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                          sa_result* results) {
-    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, nullptr, 0, true);
-}
-
-int sa_banded_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs, int* cells_per_lane,
-                         int* pairs_per_wave, uint64_t* ws_bytes_per_pair) {
-    (void)npairs;   // a pair's variant and records depend on its own shape only
-    // (the scoring-dependent checks are the calls'; a permissive scoring stands in for them here)
-    const sa_scoring any{0, 0, 0, 0, 0, 1};
-    int rc = banded_prologue(nullptr, &algo, &any, band);
-    if (rc) return rc;
-    BandGeom g;
-    int v = 0;
-    if ((rc = banded_pair_plan(nullptr, algo, &any, max_m, max_n, band, &g, &v))) return rc;
-    if (cells_per_lane) *cells_per_lane = kBandR[v];
-    if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
-    if (ws_bytes_per_pair) *ws_bytes_per_pair = band_rec_words(g, v) * 4;
-    return SA_OK;
-}
-
-int sa_align_batch_banded_affine(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                                 sa_result* results, uint8_t* ops, uint64_t ops_cap) {
-    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, false, true);
-}
-
-int sa_score_batch_banded_affine(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                                 sa_result* results) {
-    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, nullptr, 0, true, true);
-}
-
-int sa_banded_affine_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band, uint32_t npairs, int* cells_per_lane,
-                                int* pairs_per_wave, uint64_t* ws_bytes_per_pair) {
-    (void)npairs;
-    const sa_scoring any{0, 0, 0, 0, 0, 1};   // (as sa_banded_plan_query: the scoring-dependent checks are the calls')
-    int rc = banded_affine_prologue(nullptr, algo, &any, band);
-    if (rc) return rc;
-    BandGeom g;
-    int v = 0;
-    if ((rc = banded_pair_plan(nullptr, algo, &any, max_m, max_n, band, &g, &v))) return rc;
-    if (cells_per_lane) *cells_per_lane = kBandR[v];
-    if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
-    if (ws_bytes_per_pair) *ws_bytes_per_pair = band_affine_rec_words(g, v) * 4;
-    return SA_OK;
-}
-
-// sa_align_batch_banded_ends_free / sa_score_batch_banded_ends_free: the algorithm picks the band (NW's
-// or GlobalGotoh's, whose prologues make the remaining checks), then banded_batch.
-static int banded_ends_free_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                  const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                                  uint32_t free_ends, sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
-    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
-    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
-    if (free_ends > 15) return fail(c, SA_ERR_ARG, "free_ends holds bits outside SA_FREE_*");
-    if (algo != SA_NW && algo != SA_HIRSCHBERG && algo != SA_GLOBAL_GOTOH)
-        return fail(c, SA_ERR_UNSUPPORTED, "ends-free banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only");
-    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, notb,
-                        algo == SA_GLOBAL_GOTOH, nullptr, (int)free_ends);
-}
-
-int sa_align_batch_banded_ends_free(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                    const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                                    uint32_t free_ends, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
-    return banded_ends_free_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, free_ends, results, ops, ops_cap, false);
-}
-
-int sa_score_batch_banded_ends_free(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                    const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut, uint32_t band,
-                                    uint32_t free_ends, sa_result* results) {
-    return banded_ends_free_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, free_ends, results, nullptr, 0, true);
-}
-
-// sa_align_batch_banded_seeded / sa_score_batch_banded_seeded: the ends-free calls with every pair's band
-// round its seed diagonal.  Their own prologue (what the seed adds), then banded_batch, whose per-pair
-// plan applies the legality rule.
-static int banded_seeded_prologue(sa_ctx* c, int algo, const sa_scoring* sc, uint32_t band, uint32_t free_ends) {
-    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
-    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
-    if (free_ends > 15) return fail(c, SA_ERR_ARG, "free_ends holds bits outside SA_FREE_*");
-    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: 2 * band + 1 diagonals overflow 32 bits");
-    if (algo != SA_NW && algo != SA_HIRSCHBERG && algo != SA_GLOBAL_GOTOH)
-        return fail(c, SA_ERR_UNSUPPORTED, "seeded banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only");
-    return SA_OK;
-}
-
-static int banded_seed_in_matrix(sa_ctx* c, uint64_t pair, uint64_t m, uint64_t n, int32_t diag) {
-    if ((int64_t)diag < -(int64_t)m || (int64_t)diag > (int64_t)n)
-        return fail(c, SA_ERR_ARG, "pair " + std::to_string(pair) + ": seed diagonal " + std::to_string(diag) +
-                                       " does not cross the " + std::to_string(m) + " x " + std::to_string(n) + " matrix");
-    return SA_OK;
-}
-
-static int banded_seeded_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                               const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
-                               const int32_t* diag, uint32_t band, uint32_t free_ends, sa_result* results, uint8_t* ops,
-                               uint64_t ops_cap, bool notb) {
-    int rc = banded_seeded_prologue(c, algo, sc, band, free_ends);
-    if (rc) return rc;
-    if (npairs && !diag) return fail(c, SA_ERR_ARG, "diag is NULL");
-    if (off1 && off2) {
-        for (uint32_t p = 0; p < npairs; ++p) {
-            if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
-            if ((rc = banded_seed_in_matrix(c, p, off1[p + 1] - off1[p], off2[p + 1] - off2[p], diag[p]))) return rc;
-        }
-    }
-    static const int32_t none = 0;   // (npairs == 0: banded_batch still takes the seeded route)
-    return banded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, notb,
-                        algo == SA_GLOBAL_GOTOH, nullptr, (int)free_ends, diag ? diag : &none);
-}
-
-int sa_align_batch_banded_seeded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
-                                 const int32_t* diag, uint32_t band, uint32_t free_ends, sa_result* results, uint8_t* ops,
-                                 uint64_t ops_cap) {
-    return banded_seeded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, diag, band, free_ends, results, ops, ops_cap, false);
-}
-
-int sa_score_batch_banded_seeded(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* lut,
-                                 const int32_t* diag, uint32_t band, uint32_t free_ends, sa_result* results) {
-    return banded_seeded_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, lut, diag, band, free_ends, results, nullptr, 0, true);
-}
-
-int sa_banded_seeded_plan_query(int algo, uint64_t m, uint64_t n, int32_t diag, uint32_t band, uint32_t free_ends,
-                                int* cells_per_lane, int* pairs_per_wave, uint64_t* ws_bytes_per_pair) {
-    const sa_scoring any{0, 0, 0, 0, 0, 1};   // (as sa_banded_plan_query: the scoring-dependent checks are the calls')
-    int rc = banded_seeded_prologue(nullptr, algo, &any, band, free_ends);
-    if (rc) return rc;
-    if (m >= (1u << 24) || n >= (1u << 24)) return fail(nullptr, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
-    if ((rc = banded_seed_in_matrix(nullptr, 0, m, n, diag))) return rc;
-    const bool affine = algo == SA_GLOBAL_GOTOH;
-    const BandSeed sd{diag, free_ends, 0};
-    BandGeom g;
-    int v = 0;
-    if ((rc = banded_pair_plan(nullptr, affine ? algo : SA_NW, &any, m, n, band, &g, &v, &sd))) return rc;
-    if (cells_per_lane) *cells_per_lane = kBandR[v];
-    if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
-    if (ws_bytes_per_pair) *ws_bytes_per_pair = (affine ? band_affine_rec_words(g, v) : band_rec_words(g, v)) * 4;
-    return SA_OK;
-}
-
 int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,
                         int* kernel, int* R, int* W, uint64_t* ws_bytes_per_pair) {
     if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(nullptr, SA_ERR_ARG, "unknown algorithm");
@@ -2910,60 +2285,26 @@ int sa_score_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t
 // the used K x K corner of the caller's table densely; the label table (match_lut or equality) becomes
 // a bit table over codes.  run_device then runs the int32 planner's plan with that table.
 
-// Algorithm, scoring and table checks shared with sa_matrix_plan_query (c may be NULL).
-static int matrix_prologue(sa_ctx* c, int algo, const sa_scoring* sc) {
-    if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");
-    if (algo < SA_SW || algo > SA_MYERS_MILLER) return fail(c, SA_ERR_ARG, "unknown algorithm");
-    if (algo == SA_HIRSCHBERG || algo == SA_MYERS_MILLER)
-        return fail(c, SA_ERR_UNSUPPORTED, "matrix calls support SA_SW, SA_NW, SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH only");
-    return SA_OK;
-}
-
 static int matrix_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
                         const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
                         const uint8_t* lut, sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
     // (the checks that need no context come first, so they answer without a device too)
-    int rc = matrix_prologue(c, algo, sc);
+    int rc = check_call(c, kMatrixRules, algo, sc, 0, 0);
     if (rc) return rc;
     if (!submat) return fail(c, SA_ERR_ARG, "submat is NULL");
-    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
-    if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
-    if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
-    for (uint32_t p = 0; p < npairs; ++p)
-        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
+    if ((rc = check_batch_buffers(c, seq1, off1, seq2, off2, npairs, results, ops, notb))) return rc;
     const uint64_t t1 = off1[npairs], t2 = off2[npairs];
-
-    // the batch's symbols, both sides together: codes in byte order
-    bool seen[256] = {};
-    for (uint64_t k = 0; k < t1; ++k) seen[seq1[k]] = true;
-    for (uint64_t k = 0; k < t2; ++k) seen[seq2[k]] = true;
-    uint8_t code[256] = {};
-    int syms[kSubMaxSyms];
-    int K = 0;
-    for (int b = 0; b < 256; ++b)
-        if (seen[b]) {
-            if (K == kSubMaxSyms)
-                return fail(c, SA_ERR_UNSUPPORTED, "matrix calls take batches of at most " + std::to_string(kSubMaxSyms) +
-                                                       " distinct symbols (both sequence sets together)");
-            code[b] = (uint8_t)K;
-            syms[K++] = b;
-        }
-    if (K == 0) syms[K++] = 0;   // (no symbol at all: a one-entry table nobody reads)
-    // the used corner, its extremes, and the score bound: with every step of a path adding at most
-    // `big` in magnitude (a gap opening at most twice that), (m + n + 1) * big < 2^29 keeps every
-    // cell -- and the Gotoh borders of -10000 plus such a path -- inside int32
-    std::vector<int16_t> tab(kSubMaxSyms * kSubMaxSyms, 0);
-    int32_t smax = 0, smin = 0;
-    for (int a = 0; a < K; ++a)
-        for (int b = 0; b < K; ++b) {
-            const int16_t s = submat[syms[a] * 256 + syms[b]];
-            tab[a * K + b] = s;
-            smax = std::max<int32_t>(smax, s);
-            smin = std::min<int32_t>(smin, s);
-        }
+    // the batch's symbol codes and the used corner of the table (sub_recode), its extremes, and the score
+    // bound: with every step of a path adding at most `big` in magnitude (a gap opening at most twice
+    // that), (m + n + 1) * big < 2^29 keeps every cell -- and the Gotoh borders of -10000 plus such a
+    // path -- inside int32
+    SubRecode sub;
+    if ((rc = sub_recode(c, seq1, t1, seq2, t2, submat, &sub))) return rc;
+    const uint8_t* const code = sub.code;
+    const int K = sub.K;
     auto ab = [](int32_t x) { return (int64_t)(x < 0 ? -(int64_t)x : x); };
     const int64_t gapbig = is_affine(algo) ? std::max(ab(sc->gap_open), ab(sc->gap_extend)) : ab(sc->gap);
-    const int64_t big = std::max(gapbig, std::max<int64_t>(smax, -(int64_t)smin));
+    const int64_t big = std::max(gapbig, std::max<int64_t>(sub.smax, -(int64_t)sub.smin));
     uint32_t max_m = 0, max_n = 0;
     for (uint32_t p = 0; p < npairs; ++p) {
         const uint64_t m = off1[p + 1] - off1[p], n = off2[p + 1] - off2[p];
@@ -2982,10 +2323,7 @@ static int matrix_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
 
     // what run_device's host decisions read of the scoring: the diagonal term's extremes (keyed_ok
     // bounds a local score by match * min(m, n), and by the absolute values when a gap term is positive)
-    sa_scoring sc2 = *sc;
-    sc2.match = smax;
-    sc2.mismatch = smin;
-    sc2.allow_mismatch = 1;
+    const sa_scoring sc2 = sub_scoring(*sc, sub);
 
     auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
     const uint64_t b_s1 = al(t1 + 1), b_s2 = al(t2 + 1), b_o = al(8ull * (npairs + 1)), b_res = al(sizeof(sa_result) * (uint64_t)npairs);
@@ -3012,8 +2350,8 @@ static int matrix_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t
     memset(hbits, 0, 8192);
     for (int a = 0; a < K; ++a)
         for (int b = 0; b < K; ++b)
-            if (lut ? lut[syms[a] * 256 + syms[b]] != 0 : a == b) hbits[a * 8 + b / 32] |= 1u << (b % 32);
-    memcpy(htab, tab.data(), 2ull * kSubMaxSyms * kSubMaxSyms);
+            if (lut ? lut[sub.syms[a] * 256 + sub.syms[b]] != 0 : a == b) hbits[a * 8 + b / 32] |= 1u << (b % 32);
+    memcpy(htab, sub.tab.data(), 2ull * kSubMaxSyms * kSubMaxSyms);
     hipStream_t st = c->stream;
     if (t1) SA_HIP(c, hipMemcpyAsync(d1, h1, t1, hipMemcpyHostToDevice, st));
     if (t2) SA_HIP(c, hipMemcpyAsync(d2, h2, t2, hipMemcpyHostToDevice, st));
@@ -3053,78 +2391,9 @@ int sa_score_batch_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8
     return matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, results, nullptr, 0, true);
 }
 
-// sa_align_batch_banded_matrix / sa_score_batch_banded_matrix: the symbol scan, codes and dense table of
-// matrix_batch, then banded_batch (linear or affine by algorithm) with the kMatchSub fills.  The
-// per-pair score bounds are the banded calls' own, with the table's extremes in place of match /
-// mismatch -- for the affine algorithms the stricter |gap_open| + |gap_extend| form, which the
-// sentinel argument of the affine band needs.
-static int banded_matrix_batch(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                               const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
-                               const uint8_t* lut, uint32_t band, sa_result* results, uint8_t* ops, uint64_t ops_cap, bool notb) {
-    // (the checks that need no context come first, so they answer without a device too)
-    int rc = matrix_prologue(c, algo, sc);
-    if (rc) return rc;
-    const bool affine = is_affine(algo);
-    if (affine && sc->gap_extend > 0)
-        return fail(c, SA_ERR_UNSUPPORTED, "banded affine calls need gap_extend <= 0 (the records decide the walk only then)");
-    if (band >= 0x80000000u) return fail(c, SA_ERR_ARG, "band: |n - m| + 2 * band + 1 diagonals overflow 32 bits");
-    if (!submat) return fail(c, SA_ERR_ARG, "submat is NULL");
-    if (!off1 || !off2 || (npairs && (!results || (!notb && !ops)))) return fail(c, SA_ERR_ARG, "NULL buffer");
-    if ((off1[npairs] && !seq1) || (off2[npairs] && !seq2)) return fail(c, SA_ERR_ARG, "NULL sequence buffer");
-    if (off1[0] != 0 || off2[0] != 0) return fail(c, SA_ERR_ARG, "offsets must start at 0");
-    for (uint32_t p = 0; p < npairs; ++p)
-        if (off1[p + 1] < off1[p] || off2[p + 1] < off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
-    const uint64_t t1 = off1[npairs], t2 = off2[npairs];
-
-    // the batch's symbols, both sides together: codes in byte order (as matrix_batch)
-    BandSub sub;
-    bool seen[256] = {};
-    for (uint64_t k = 0; k < t1; ++k) seen[seq1[k]] = true;
-    for (uint64_t k = 0; k < t2; ++k) seen[seq2[k]] = true;
-    memset(sub.code, 0, sizeof(sub.code));
-    int K = 0;
-    for (int b = 0; b < 256; ++b)
-        if (seen[b]) {
-            if (K == kSubMaxSyms)
-                return fail(c, SA_ERR_UNSUPPORTED, "matrix calls take batches of at most " + std::to_string(kSubMaxSyms) +
-                                                       " distinct symbols (both sequence sets together)");
-            sub.code[b] = (uint8_t)K;
-            sub.syms[K++] = b;
-        }
-    if (K == 0) sub.syms[K++] = 0;   // (no symbol at all: a one-entry table, so that no lane indexes outside it)
-    sub.K = K;
-    sub.tab.assign(kSubMaxSyms * kSubMaxSyms, 0);
-    int32_t smax = 0, smin = 0;
-    for (int a = 0; a < K; ++a)
-        for (int b = 0; b < K; ++b) {
-            const int16_t s = submat[sub.syms[a] * 256 + sub.syms[b]];
-            sub.tab[a * K + b] = s;
-            smax = std::max<int32_t>(smax, s);
-            smin = std::min<int32_t>(smin, s);
-        }
-    // what banded_pair_plan reads of the scoring: the diagonal term's extremes
-    sa_scoring sc2 = *sc;
-    sc2.match = smax;
-    sc2.mismatch = smin;
-    sc2.allow_mismatch = 1;
-    return banded_batch(c, algo, &sc2, seq1, off1, seq2, off2, npairs, lut, band, results, ops, ops_cap, notb, affine, &sub);
-}
-
-int sa_align_batch_banded_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
-                                 const uint8_t* match_lut, uint32_t band, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
-    return banded_matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, band, results, ops, ops_cap, false);
-}
-
-int sa_score_batch_banded_matrix(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1,
-                                 const uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const int16_t* submat,
-                                 const uint8_t* match_lut, uint32_t band, sa_result* results) {
-    return banded_matrix_batch(c, algo, sc, seq1, off1, seq2, off2, npairs, submat, match_lut, band, results, nullptr, 0, true);
-}
-
 int sa_matrix_plan_query(int algo, const sa_scoring* sc, uint32_t max_m, uint32_t max_n, uint32_t npairs, int nsym,
                          int* kernel, int* rows_per_lane, int* waves, uint64_t* workspace_bytes_per_pair) {
-    int rc = matrix_prologue(nullptr, algo, sc);
+    int rc = check_call(nullptr, kMatrixRules, algo, sc, 0, 0);   // (algorithm and scoring: as the calls)
     if (rc) return rc;
     if (nsym < 0) return fail(nullptr, SA_ERR_ARG, "nsym is negative");
     if (nsym > kSubMaxSyms)
