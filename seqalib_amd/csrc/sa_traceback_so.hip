@@ -367,6 +367,15 @@ __global__ __launch_bounds__(64) void traceback_so_kernel(TbParams P) {
 // A lone wave's serial recompute per block drops from 32 columns x R rows of dependent cells to
 // (32 + 3) sub-steps x R/4 rows, and the wave's registers (R/4 rows of state) stay few, so the
 // traceback beside the next call's fill displaces fewer of its waves.
+// The kernel runs beside a fill that is bound by VALU issue, so what it costs that fill is its own
+// VALU count, and the loops carry little besides the cells (the VALU diet):
+//   * a sub-step reads one LDS word for its column (8 x code | the row above << 16), staged per
+//     round from the edge packets with the border values folded in, one sub-step ahead at an
+//     address that only increments; it stores each cell's tag as the low byte of the tagged value
+//     (ds_write_b8 at an immediate offset: no pack, no select, no shift of packed codes);
+//   * the walk reads the codes of the row above and the column to the left with the three tags of
+//     the cells it may move to (one LDS round trip per move), takes its op letter, score and step
+//     from the tag's bits by arithmetic, and stores the op through the wave's base + a 32-bit offset.
 // Lanes per pair: 4 (16 pairs per wave) for pipelined calls, whose traceback runs beside the next
 // call's fill: half the waves of 8 lanes per pair, pipelined headline step 18.4 -> 17.9 ms (round 5,
 // profiles/tb_lp_ab_r05.txt); 8 for a call nothing else overlaps, where the traceback alone sets the
@@ -391,17 +400,32 @@ extern "C" int sa_debug_so4_stats(unsigned long long* out, int reset) {
 template <int R, int LP>
 struct So4Lds {
     static constexpr int kPairs = kWave / LP;                 // pairs per wave
-    // [quad][column q][row r] bytes (1 KiB per quad, the cell's tag in bits 0-1); 64 B of pad in
-    // front: the walk reads the three cells up-left of its cell, also from a block's first row
-    // quads are 1 KiB + 32 B apart so the quads' tag stores land on different banks (at 1 KiB the
-    // same column's stores of every quad of the wave hit the same 8 banks)
+    // [quad][column q][row r] bytes (1 KiB per quad, the cell's tag in bits 0-1: the low byte of the
+    // cell's tagged value, stored as it is); 64 B of pad in front: the walk reads the three cells
+    // up-left of its cell, also from a block's first row.  Quads are 1 KiB + 32 B apart: a sub-step
+    // stores one byte per row (ds_write_b8, offset r), sublane k of quad g at column q at bank
+    // 8 (g + q) + (k RS + r) / 4 (mod 32), so the four sublanes of a quad (columns q .. q - 3) never
+    // share a bank and two quads do only when g + q agree mod 4: 2-way within a 32-lane group when
+    // the quads sweep in step (at 1 KiB every quad's stores of a column hit the same 8 banks).
     static constexpr int kTags = 64;
     static constexpr int kQuad = 1024 + 32;
     static constexpr int kEdge = kTags + kPairs * kQuad;       // [lane] 16 B: packet (sub) of the quad
     static constexpr int kEdge2 = kEdge + 64 * 16;            // LP = 4: [lane] 16 B: packet 4 (sublane 0)
-    static constexpr int kRowC = kEdge2 + (LP < 5 ? 64 * 16 : 0);   // [quad][32] row codes (8 x code)
-    static constexpr int kColC = kRowC + kPairs * 32;         // [quad][32] column codes
-    static constexpr int kBytes = kColC + kPairs * 32;
+    // the walk's codes, one byte per row / column (the byte before a quad's first one is read, never used)
+    static constexpr int kRowC = kEdge2 + (LP < 5 ? 64 * 16 : 0);   // [quad][32] 4 x row code
+    static constexpr int kColC = kRowC + kPairs * 32;         // [quad][32] column code
+    // the sub-steps' column words, [quad][kTopW]: word LP + q = 8 x code of column q | 4 H of the row
+    // above the block at column q << 16 (the border value where the block has no row above).  A lane
+    // reads one word per sub-step at an address that only increments, from LP - 1 words before its
+    // quad's first column to, for a quad that has finished while the wave's widest has not, 2 x 32 +
+    // 2 LP words past it: the pad in front, the next quads' rows and the tail keep that inside the
+    // allocation.  Rows are 52 (LP = 4) / 56 (LP = 8) words apart: the LP consecutive words the quads
+    // of a 32-lane group read then fall on 32 different banks when the quads sweep in step.
+    static constexpr int kTopW = LP == 4 ? 52 : 56;
+    static constexpr int kTopTail = 64;
+    static constexpr int kTop = kColC + kPairs * 32;
+    static constexpr int kBytes = kTop + (kPairs * kTopW + kTopTail) * 4;
+    static_assert(LP + 31 + 32 + LP + 1 < kTopW + kTopTail, "the last quad's read-ahead stays inside");
 };
 
 // ALG: SA_SW (SASmithWaterman.h:220-339, from the end cell, stops at H == 0) or SA_NW
@@ -418,9 +442,7 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
     typedef volatile uint8_t __attribute__((address_space(3))) lds_u8;
     typedef volatile uint32_t __attribute__((address_space(3))) lds_u32;
     typedef volatile uint16_t __attribute__((address_space(3))) lds_u16;
-    typedef volatile uint64_t __attribute__((address_space(3))) lds_u64;
     lds_u8* const vb = (lds_u8*)s_so;
-    lds_u32* const vw = (lds_u32*)s_so;
     const int lane = threadIdx.x, quad = lane / LP, sub = lane % LP;
     const uint32_t slot = blockIdx.x * L::kPairs + quad;
     // a quad whose pair is not walked here leaves as a whole (the four lanes agree)
@@ -440,7 +462,14 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
     const uint8_t* s1 = P.seq1 + o1;
     const uint8_t* s2 = P.seq2 + o2;
     typedef uint8_t __attribute__((address_space(1))) glb_u8;
-    glb_u8* ops = (glb_u8*)(P.ops + o1 + o2 + pidx);
+    // op bytes go through a base the wave shares (the op stream of its first pair: the grid has no
+    // wave without one) plus a 32-bit offset, so a store needs no 64-bit per-lane address (the
+    // streams of a wave's <= 16 pairs, m + n + 1 bytes each, are far from 4 GiB on any shape a
+    // full-matrix fill can take)
+    const uint32_t pidx0 = P.pair_base + blockIdx.x * (uint32_t)L::kPairs;
+    const uint64_t obase = P.off1[pidx0] + P.off2[pidx0] + pidx0;
+    glb_u8* const ops = (glb_u8*)(P.ops + obase);
+    const uint32_t ooff = (uint32_t)(o1 + o2 + pidx - obase);
     const uint8_t* const dir = P.dirs + (uint64_t)(live ? slot : 0) * P.dir_slot;
     const uint64_t band_stride = P.band_stride;
     const uint32_t npk = (uint32_t)(band_stride / (kWave * 16));
@@ -458,8 +487,10 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
             const bool v = P.lutbits ? ((P.lutbits[(sa_ << 3) | (sb_ >> 5)] >> (sb_ & 31u)) & 1u) != 0 : sa_ == sb_;
             mt |= (v ? 1u : 0u) << (a * 4 + b);
         }
-    const bool allow = P.allow != 0;
     const int G = P.gap, MA = P.match, MI = P.mismatch;
+    // the walk's op letter by tag (0, 1: left; 2: up; 3: diagonal, a mismatch -- a match adds kOpM)
+    const uint32_t optab = 'L' | 'L' << 8 | 'U' << 16 | (uint32_t)(P.allow != 0 ? 'S' : 'X') << 24;
+    const uint32_t kOpM = (uint32_t)'M' - (optab >> 24);
     // up term: SW max(4U + 2, 0) by unsigned saturation, NW 4U + 2 (no clamp)
     const uint32_t CU = (uint32_t)(NWK ? 4 * G + 2 : -(4 * G + 2)) & 0xffffu;
     const uint32_t CL = (uint32_t)(4 * G + 1) & 0xffffu;
@@ -470,7 +501,7 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
 
     uint32_t k = 0;
     auto emit = [&](uint8_t op) __attribute__((always_inline)) {
-        if (sub == 0) ops[k] = op;   // (a store in flight costs the walk nothing)
+        if (sub == 0) ops[ooff + k] = op;   // (a store in flight costs the walk nothing)
         ++k;
     };
     int cb = 0, ct = 0, cc = 0, cr = 0, cq = 0;
@@ -483,20 +514,6 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
         const int s = j - 1 + ct;
         cc = s >> 5;
         cq = s & 31;
-    };
-    // the walk's view of the block: the quad's R row codes and 32 column codes (2 bits each) in
-    // registers; the move tags stay in LDS ([column q][lane] words, sublane r / RS, bits 2 (r % RS))
-    uint64_t rowc = 0, colc = 0;
-    auto pack_codes = [&](int base) __attribute__((always_inline)) -> uint64_t {   // 32 bytes of 8 x code
-        uint64_t c = 0;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            uint32_t x = (vw[(base >> 2) + d] >> 3) & 0x03030303u;   // four codes, one per byte
-            x = (x | (x >> 6)) & 0x000f000fu;
-            x = (x | (x >> 12)) & 0xffu;
-            c |= (uint64_t)x << (8 * d);
-        }
-        return c;
     };
     // recompute the block holding (i, j), columns up to j; every lane of a live quad takes part
     // (a finished or dead quad runs the same sub-step loop on a zero-width column range)
@@ -540,9 +557,11 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
         // this sublane's rows: left column, corner (the row above its first row, column j0 - 1)
         int Hp[RS];
         int corner = 0;
-        uint32_t tab[RS];
+        uint32_t tab[RS], cw[32 / LP];   // (cw: 8 x code of this sublane's columns)
 #pragma unroll
         for (int r = 0; r < RS; ++r) { Hp[r] = 0; tab[r] = pf0; }
+#pragma unroll
+        for (int x = 0; x < 32 / LP; ++x) cw[x] = 0;
         if (act) {
             const int rs0 = sub * RS;   // block-relative first row
             // Every load of the block's inputs is issued before any value is used, so a round pays one
@@ -581,15 +600,42 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
             for (int r = 0; r < RS; ++r) {
                 const uint32_t c8 = r0 + rs0 + r < m ? so_code8(symp, b1[r]) : 0u;
                 tab[r] = c8 == 0 ? pf0 : c8 == 8 ? pf1 : c8 == 16 ? pf2 : pf3;
-                vb[L::kRowC + quad * 32 + rs0 + r] = (uint8_t)c8;
+                vb[L::kRowC + quad * 32 + rs0 + r] = (uint8_t)(c8 >> 1);
             }
 #pragma unroll
             for (int x = 0; x < 32 / LP; ++x) {
                 const int q = sub * (32 / LP) + x, jj = j0 + q;
-                vb[L::kColC + quad * 32 + q] = (uint8_t)(q >= qlo && q <= qhi && jj < n ? so_code8(symp, b2[x]) : 0u);
+                cw[x] = q >= qlo && q <= qhi && jj < n ? so_code8(symp, b2[x]) : 0u;
+                vb[L::kColC + quad * 32 + q] = (uint8_t)(cw[x] >> 3);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the edge DMA and the code stores
+        // the column words of this sublane's 32 / LP columns: the step of column q is slo + q and slo
+        // = 7 (mod 8) (32 c - 1, or 32 c + 63 under lane 0), so column q is value (q + 7) % 8 of the
+        // row's packet (q + 7) / 8.  (A packet outside the band was not loaded: its columns are outside
+        // qlo .. qhi and their words are never used.)
+        if (act) {
+            constexpr int NX = 32 / LP;
+            const uint32_t wtop = (uint32_t)(L::kTop + (quad * L::kTopW + LP + sub * NX) * 4);
+            uint32_t e0, e1;   // LDS addresses of column sub * NX's value and of the one after it
+            if constexpr (LP == 4) {
+                e0 = (uint32_t)(L::kEdge + lane * 16 + 14);
+                e1 = sub < 3 ? (uint32_t)(L::kEdge + (lane + 1) * 16) : (uint32_t)(L::kEdge2 + quad * 64);
+            } else {
+                const int s7 = sub * NX + 7;
+                e0 = (uint32_t)(L::kEdge + (quad * LP + (s7 >> 3)) * 16 + (s7 & 7) * 2);
+                e1 = (sub & 1) ? e0 + 2 : (uint32_t)(L::kEdge + (quad * LP + (s7 >> 3) + 1) * 16);
+            }
+            uint32_t ev[NX];   // (every read before the first store: one LDS round trip, not NX)
+#pragma unroll
+            for (int x = 0; x < NX; ++x) ev[x] = *(lds_u16*)(s_so + (x == 0 ? e0 : e1 + (uint32_t)(x - 1) * 2));
+#pragma unroll
+            for (int x = 0; x < NX; ++x) {
+                uint32_t top = ev[x] << 18;      // 4 H in the high half
+                if (!has_top) top = NWK ? (uint32_t)border(j0 + sub * NX + x + 1) << 16 : 0u;   // row 0: H(0, j) = j * Gap (NW), 0 (SW)
+                *(lds_u32*)(s_so + wtop + x * 4) = cw[x] | top;
+            }
+        }
 #ifdef SA_TB_STATS
         {
             const unsigned long long t = __builtin_amdgcn_s_memtime();
@@ -597,74 +643,53 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
             st_a = t;
         }
 #endif
-        // sub-steps: sublane k at column qlo + u - k; its row above from sublane k-1 (DPP).  The
-        // column codes come from the quad's packed 2-bit codes (registers), sublane 0's top-row value
-        // of the next sub-step is read one sub-step ahead from an always-valid LDS address, so a
-        // sub-step neither branches round an LDS read nor waits for one.
-        if (act) colc = pack_codes(L::kColC + quad * 32);   // (in-order LDS: the codes stored above)
+        // sub-steps: sublane k at column qlo + u - k; its row above from sublane k-1 (DPP).  A lane
+        // reads its column's word (8 x code | row above << 16) one sub-step ahead, at an address that
+        // only increments (So4Lds::kTop), so a sub-step neither branches round an LDS read nor waits
+        // for one, and computes no address or select for it.
         int hl = Hp[RS - 1];
         int prev_up = corner;
         int nmax = qhi - qlo + 1 + (LP - 1);   // sub-steps of this quad; the wave runs the most of any
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) nmax = max(nmax, __shfl_xor(nmax, off));
-        auto rd_top = [&](int q) __attribute__((always_inline)) -> int {   // (used by sublane 0 only)
-            const int s = slo + q;
-            const int d = min(max((s >> 3) - pk0, 0), 4);
-            const int off = (LP >= 5 || d < 4) ? L::kEdge + (quad * LP + d) * 16 : L::kEdge2 + quad * 64;
-            const int v = (int)((lds_u16*)(s_so + off + (s & 7) * 2))[0] << 2;
-            return has_top ? v : NWK ? border(j0 + q + 1) : 0;   // row 0: H(0, j) = j * Gap (NW), 0 (SW)
-        };
-        int ntop = rd_top(qlo);
-        for (int u = 0; u < nmax; ++u) {
-            const int q = qlo + u - sub;
-            const int top = ntop;
-            ntop = rd_top(qlo + u + 1);
-            const uint32_t sym = (uint32_t)((colc >> (2 * (q & 31))) & 3u) << 3;
+        const uint32_t ncol = (uint32_t)(qhi - qlo + 1);   // columns of this quad (0: none, also when !act)
+        uint32_t wa = (uint32_t)(L::kTop + (quad * L::kTopW + LP + qlo - sub) * 4);   // word of column qlo - sub
+        uint32_t tpo = (uint32_t)(L::kTags + quad * L::kQuad + (qlo - sub) * 32 + sub * RS);   // tags of that column, this sublane's rows
+        uint32_t wn = *(lds_u32*)(s_so + wa);
+        for (int u = 0; u < nmax; ++u, tpo += 32) {
+            const uint32_t sym = wn;             // (v_bfe_i32 takes the code from bits 3-4 as its offset)
+            wa += 4;
+            wn = *(lds_u32*)(s_so + wa);
             // the row above from sublane k-1: quad_perm [0,0,1,2] (LP = 4) / row_shr:1 (LP = 8; the
             // sublane 0 lanes, which take lane 7 of the previous group, use the top row instead)
             int up_h = LP == 4 ? __builtin_amdgcn_mov_dpp(hl, 0x90, 0xf, 0xf, false)
                                : __builtin_amdgcn_mov_dpp(hl, 0x111, 0xf, 0xf, false);
-            const bool on = act && q >= qlo && q <= qhi;
-            if (sub == 0) up_h = top;
+            const bool on = (uint32_t)(u - sub) < ncol;
+            if (sub == 0) up_h = (int)(sym >> 16);
             if (on) {
                 uint32_t dcur;
                 asm("v_bfe_i32 %0, %1, %2, 8\n\tv_add_u16 %0, %3, %0" : "=&v"(dcur) : "v"(tab[0]), "v"(sym), "v"(prev_up));
                 uint32_t hu = (uint32_t)up_h;
-                uint32_t rec[(RS + 3) / 4];   // row r's tagged value, low byte, at byte r % 4 of word r / 4
-#pragma unroll
-                for (int w = 0; w < (RS + 3) / 4; ++w) rec[w] = 0;
 #pragma unroll
                 for (int r = 0; r < RS; ++r) {
                     uint32_t a0, a1, adn;
-                    // v_perm_b32 selector: byte r % 4 from a0's byte 0, the others kept
-                    const uint32_t kSel = (r % 4 == 0) ? 0x03020104u : (r % 4 == 1) ? 0x03020400u
-                                            : (r % 4 == 2) ? 0x03040100u : 0x04020100u;
 #define SO4_CELL(UP)                                                                               \
     asm("v_add_u16 %[a0], %[cl], %[hp]\n\t"                                                         \
         "v_bfe_i32 %[adn], %[tabn], %[sym], 8\n\t"                                                  \
         "v_add_u16 %[adn], %[hp], %[adn]\n\t" UP                                                   \
         "v_max_i16 %[a0], %[dr], %[a0]\n\t"                                                         \
         "v_max_i16 %[a0], %[a1], %[a0]\n\t"                                                         \
-        "v_and_b32 %[hp], -4, %[a0]\n\t"                                                            \
-        "v_perm_b32 %[rec], %[a0], %[rec], %[sel]"                                                 \
-        : [a0] "=&v"(a0), [a1] "=&v"(a1), [adn] "=&v"(adn), [hp] "+v"(Hp[r]), [rec] "+v"(rec[r / 4]) \
+        "v_and_b32 %[hp], -4, %[a0]"                                                                \
+        : [a0] "=&v"(a0), [a1] "=&v"(a1), [adn] "=&v"(adn), [hp] "+v"(Hp[r])                        \
         : [dr] "v"(dcur), [hu] "v"(hu), [cu] "s"(CU), [cl] "s"(CL),                                 \
-          [tabn] "v"(tab[r + 1 < RS ? r + 1 : r]), [sym] "v"(sym), [sel] "s"(kSel))
+          [tabn] "v"(tab[r + 1 < RS ? r + 1 : r]), [sym] "v"(sym))
                     if constexpr (NWK) SO4_CELL("v_add_u16 %[a1], %[cu], %[hu]\n\t");
                     else SO4_CELL("v_sub_u16_e64 %[a1], %[hu], %[cu] clamp\n\t");
 #undef SO4_CELL
+                    // the cell's tag: the low byte of its tagged value, byte [quad][q][sub * RS + r]
+                    vb[tpo + r] = (uint8_t)a0;
                     dcur = adn;
                     hu = (uint32_t)Hp[r];
-                }
-                // the sublane's RS rows of column q: contiguous bytes of the quad's column
-                const uint32_t tpo = (uint32_t)(L::kTags + quad * L::kQuad + q * 32 + sub * RS);
-                if constexpr (RS == 1) vb[tpo] = (uint8_t)rec[0];
-                else if constexpr (RS == 2) *(lds_u16*)(s_so + tpo) = (uint16_t)rec[0];
-                else if constexpr (RS == 4) *(lds_u32*)(s_so + tpo) = rec[0];
-                else if constexpr (RS == 8) *(lds_u64*)(s_so + tpo) = (uint64_t)rec[1] << 32 | rec[0];
-                else {
-#pragma unroll
-                    for (int w = 0; w < RS / 4; ++w) ((lds_u32*)(s_so + tpo))[w] = rec[w];
                 }
                 prev_up = up_h;
                 hl = Hp[RS - 1];
@@ -674,7 +699,6 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
         st_sub += __builtin_amdgcn_s_memtime() - st_a;
         st_nsub += (unsigned long long)nmax;
 #endif
-        if (act) rowc = pack_codes(L::kRowC + quad * 32);
     };
 
     int i = res.end_i, j = res.end_j, V = res.score;
@@ -682,14 +706,15 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
     bool fin = !live, parked = true;
     // the tag of block cell (r, q): byte [quad][q][r] of the tags (bits 0-1)
     const uint32_t tag_base = (uint32_t)(L::kTags + quad * L::kQuad);
+    const uint32_t rowc_base = (uint32_t)(L::kRowC + quad * 32), colc_base = (uint32_t)(L::kColC + quad * 32);
     auto tag_at = [&](int r, int q) __attribute__((always_inline)) -> uint32_t {
         return (uint32_t)vb[tag_base + (uint32_t)q * 32u + (uint32_t)r] & 3u;
     };
     // Rounds: recompute the block of every unfinished walk (all lanes: the sub-steps use DPP across
     // the quad), then each quad's sublane 0 walks its block alone, one move per iteration from the
-    // tags in LDS.  The three cells a move can reach next (up, left, diagonal) are read while the
-    // current move is decided, so an iteration waits for one LDS round trip at most, not for the
-    // quad's LP tag words of a whole column.
+    // tags in LDS.  The three cells a move can reach next (up, left, diagonal) and the codes of the
+    // row above and the column to the left are read while the current move is decided, so an
+    // iteration waits for one LDS round trip at most.
     const int lead = quad * LP;
     for (;;) {
         // the walk's state lives in sublane 0: the quad's other lanes take it for the recompute
@@ -709,6 +734,7 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
         // (cr, cq): the walk's cell in the block (recompute located it); a move that takes either
         // below 0 leaves the block.  One exit test per move, no branch inside (sublane 0 only runs here).
         uint32_t f = tag_at(max(cr, 0), max(cq, 0));
+        uint32_t ca = vb[rowc_base + (uint32_t)max(cr, 0)], cb2 = vb[colc_base + (uint32_t)max(cq, 0)];   // 4 x row code, column code
         for (;;) {
 #ifdef SA_TB_STATS
             ++st_iters;
@@ -717,20 +743,24 @@ __global__ __launch_bounds__(64) void traceback_so4_kernel(TbParams P) {
             if (!((i > 0) & (j > 0) & (NWK | (V != 0)) & (cr >= 0) & (cq >= 0))) break;
             // the three cells the next move may reach, from one address: diagonal (r - 1, q - 1) at
             // +0, left (r, q - 1) at +1, up (r - 1, q) at +32 (a move out of the block parks; the pad
-            // in front of the tags keeps those reads inside the LDS allocation)
+            // in front of the tags keeps those reads inside the LDS allocation), and with them the
+            // codes of the row above and the column to the left
             const uint32_t a3 = tag_base + (uint32_t)(cq * 32 + cr) - 33u;
             const uint32_t fd = (uint32_t)vb[a3] & 3u, fl = (uint32_t)vb[a3 + 1] & 3u, fu = (uint32_t)vb[a3 + 32] & 3u;
-            const bool dg = f == 3u, up = f == 2u;
-            const uint32_t ca = (uint32_t)(rowc >> (2 * cr)) & 3u, cb2 = (uint32_t)(colc >> (2 * cq)) & 3u;
-            const bool v = dg & (((mt >> (ca * 4 + cb2)) & 1u) != 0);
-            ops[k++] = dg ? (v ? 'M' : (allow ? 'S' : 'X')) : (up ? 'U' : 'L');
-            V -= dg ? (v ? MA : MI) : G;
-            const int di = (dg | up) ? 1 : 0, dj = up ? 0 : 1;
-            i -= di;
-            j -= dj;
-            cr -= di;
-            cq -= dj;
-            f = dg ? fd : up ? fu : fl;
+            const uint32_t cap = vb[rowc_base + (uint32_t)cr - 1u], cbp = vb[colc_base + (uint32_t)cq - 1u];
+            // the move as arithmetic on the tag's bits: di = diagonal or up, dg = diagonal, vm = a
+            // diagonal move onto a match (letter, score and step need no select)
+            const uint32_t di = f >> 1, dg = f & di, dj = (di ^ dg) ^ 1u;
+            const uint32_t vm = dg & (mt >> (ca | cb2));
+            ops[ooff + k++] = (uint8_t)((optab >> (8 * f)) + vm * kOpM);
+            V -= G + __mul24((int)dg, MI - G) + __mul24((int)vm, MA - MI);   // (a T16 plan's scores are 16-bit)
+            i -= (int)di;
+            j -= (int)dj;
+            cr -= (int)di;
+            cq -= (int)dj;
+            f = dg ? fd : di ? fu : fl;
+            ca = di ? cap : ca;
+            cb2 = dj ? cbp : cb2;
         }
         if (!((i > 0) & (j > 0) & (NWK | (V != 0)))) fin = true;
         else parked = true;
