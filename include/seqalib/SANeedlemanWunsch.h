@@ -95,7 +95,43 @@ public:
     // Extension: H[m][n] of the last alignment.
     ScoreSystemType getScore() const { return LastScore; }
 
+    // Extension: banded X-drop extension (sa_align_batch_banded_extend / sa_score_batch_banded_extend): banded NW
+    // anchored at the first symbols of both sequences, inside `band` diagonals either side of the main one,
+    // ending at the cell of its best score; a pair whose score falls more than xdrop below its best is
+    // abandoned there (SA_XDROP_OFF: never).  The aligned prefix is padded with the unextended tails the way
+    // forceGlobal pads a local alignment; getScore() is the extension's score.  Names of their own, because
+    // (pairs, band, int) would collide with the ends-free overload.  std::runtime_error after setSubstitution()
+    // and for every status but SA_OK (xdrop < -1 among them).
+    std::vector<AlignedSequence<Ty, Blank>> getExtensions(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                          size_t band, int xdrop) {
+        std::vector<sa_result> res;
+        auto out = seqalib::detail::run<SA_NW, NeedlemanWunschSA, ContainerType, Ty, Blank>(
+            *this, pairs, res, seqalib::detail::band_of(band), seqalib::detail::kNoFreeEnds, nullptr, (long long)xdrop);
+        if (!res.empty()) LastScore = res.back().score;
+        return out;
+    }
+    std::vector<ScoreSystemType> getExtensionScores(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band,
+                                                    int xdrop) {
+        std::vector<ScoreSystemType> out;
+        for (auto& r : extensionResults(pairs, band, xdrop)) out.push_back(r.score);
+        return out;
+    }
+    // (end_i, end_j) of every pair: the last row-major cell holding the extension's maximum, (0, 0) if none is positive.
+    std::vector<std::pair<size_t, size_t>> getExtensionEndCells(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
+                                                                size_t band, int xdrop) {
+        std::vector<std::pair<size_t, size_t>> out;
+        for (auto& r : extensionResults(pairs, band, xdrop)) out.emplace_back((size_t)r.end_i, (size_t)r.end_j);
+        return out;
+    }
+
 private:
+    std::vector<sa_result> extensionResults(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, size_t band, int xdrop) {
+        std::vector<sa_result> res;
+        seqalib::detail::run_scores<SA_NW, NeedlemanWunschSA, ContainerType, Ty>(*this, pairs, res, seqalib::detail::band_of(band),
+                                                                     seqalib::detail::kNoFreeEnds, nullptr, (long long)xdrop);
+        if (!res.empty()) LastScore = res.back().score;
+        return res;
+    }
     std::vector<AlignedSequence<Ty, Blank>> alignBatch(const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
                                                        long long band, long long free_ends = seqalib::detail::kNoFreeEnds) {
         std::vector<sa_result> res;

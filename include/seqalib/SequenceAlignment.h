@@ -193,7 +193,8 @@ constexpr size_t kChunkPairs = SIZE_MAX;
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty, Ty Blank>
 std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
                                             std::vector<sa_result>& res, long long band = kNoBand,
-                                            long long free_ends = kNoFreeEnds, const std::vector<int32_t>* diags = nullptr) {
+                                            long long free_ends = kNoFreeEnds, const std::vector<int32_t>* diags = nullptr,
+                                            long long xdrop = kNoExtend) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
@@ -208,8 +209,10 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
             // (align() throws for it once the GPU call returns)
             if (r.flags & (SA_FLAG_DIVERGED | SA_FLAG_TIMEOUT)) continue;
             build_from_ops<Ty, Blank>(*pairs[p].first, *pairs[p].second, r, ops.data() + off[p], out[p]);
-            // (an ends-free alignment is padded like a local one: its free ends against Blanks)
-            const bool local = ((ALGO == SA_SW || ALGO == SA_LOCAL_GOTOH) && !(r.flags & SA_FLAG_SIZE_HACK)) || free_ends != kNoFreeEnds;
+            // (an ends-free alignment is padded like a local one: its free ends against Blanks; so is an
+            // extension: its unextended tails)
+            const bool local = ((ALGO == SA_SW || ALGO == SA_LOCAL_GOTOH) && !(r.flags & SA_FLAG_SIZE_HACK)) || free_ends != kNoFreeEnds ||
+                               xdrop != kNoExtend;
             if (local)
                 self.forceGlobal(*pairs[p].first, *pairs[p].second, out[p], r.start_i, r.start_j, r.end_i, r.end_j);
         }
@@ -224,7 +227,7 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
     // (a banded call is one range, and so is a matrix call)
     const size_t G = band == kNoBand && !sub && cp <= P / 2 ? (P + cp - 1) / cp : 1;
     if (G == 1) {
-        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub, free_ends, diags);
+        align<Ty>(ALGO, sc, fn, has_fn, pairs, res, ops, off, 0, nullptr, band, sub, free_ends, diags, xdrop);
         build_range(0, P);
         tm.lap("AlignedSequence lists");
         return out;
@@ -287,14 +290,15 @@ std::vector<AlignedSequence<Ty, Blank>> run(Aligner& self, const std::vector<std
 template <int ALGO, typename Aligner, typename ContainerType, typename Ty>
 void run_scores(Aligner& self, const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
                 std::vector<sa_result>& res, long long band = kNoBand, long long free_ends = kNoFreeEnds,
-                const std::vector<int32_t>* diags = nullptr) {
+                const std::vector<int32_t>* diags = nullptr, long long xdrop = kNoExtend) {
     auto fn = self.getMatchOperation();
     const bool has_fn = !(fn == nullptr);
     const sa_scoring sc = self.getScoring().toC();
     res.clear();
     const std::function<ScoreSystemType(Ty, Ty)>* sub = self.getSubstitution() ? &self.getSubstitution() : nullptr;
     diags_arg(diags, pairs.size(), free_ends);   // (a size mismatch throws for an empty batch too)
-    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub, free_ends, diags);
+    if (xdrop != kNoExtend) xdrop_arg(xdrop, band, sub != nullptr);   // (throws for an empty batch too)
+    if (!pairs.empty()) score<Ty>(ALGO, sc, fn, has_fn, pairs, res, band, sub, free_ends, diags, xdrop);
 }
 
 }  // namespace detail

@@ -415,6 +415,15 @@ inline const int32_t* diags_arg(const std::vector<int32_t>* diags, size_t npairs
         throw std::runtime_error("seqalib: " + std::to_string(diags->size()) + " seed diagonals for " + std::to_string(npairs) + " pairs");
     return diags->data();
 }
+// xdrop != kNoExtend: the banded extension call (sa_align_batch_banded_extend / sa_score_batch_banded_extend) with
+// this xdrop (SA_XDROP_OFF included); it needs a band and takes match / mismatch scorings only.
+constexpr long long kNoExtend = -(1LL << 40);
+inline int32_t xdrop_arg(long long xdrop, long long band, bool sub) {
+    if (band == kNoBand) throw std::runtime_error("seqalib: an extension needs a band");
+    if (sub) throw std::runtime_error("seqalib: substitution scoring and an extension cannot be combined");
+    if (xdrop < INT32_MIN || xdrop > INT32_MAX) throw std::runtime_error("seqalib: xdrop does not fit 32 bits");
+    return (int32_t)xdrop;
+}
 inline void banded_needs_table(bool overflow) {
     if (overflow)
         throw std::runtime_error("seqalib: banded calls take batches of at most " + std::to_string(kBandedMaxSymbols) +
@@ -455,9 +464,10 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs,
            std::vector<sa_result>& res, raw_vector<uint8_t>& ops, std::vector<uint64_t>& ops_off,
            uint32_t chunks = 0, ChunkFn on_chunk = nullptr, long long band = kNoBand, const SubFnTy* sub = nullptr,
-           long long free_ends = kNoFreeEnds, const std::vector<int32_t>* diags = nullptr) {
+           long long free_ends = kNoFreeEnds, const std::vector<int32_t>* diags = nullptr, long long xdrop = kNoExtend) {
     const uint32_t fe = free_ends == kNoFreeEnds ? 0 : free_ends_arg(free_ends, band, sub != nullptr);
     const int32_t* dg = diags_arg(diags, pairs.size(), free_ends);
+    const int32_t xd = xdrop == kNoExtend ? 0 : xdrop_arg(xdrop, band, sub != nullptr);
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -508,7 +518,12 @@ void align(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
     ops_off.resize(n);
     for (uint32_t p = 0; p < n; ++p) ops_off[p] = o1[p] + o2[p] + p;
     tm.lap("match table + buffers");
-    if (diags) {
+    if (xdrop != kNoExtend) {
+        check(sa_align_batch_banded_extend(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                           has_fn ? lut.data() : nullptr, band_arg(band), xd, res.data(), ops.data(), cap),
+              "sa_align_batch_banded_extend");
+        if (on_chunk && n) on_chunk(0, n);
+    } else if (diags) {
         check(sa_align_batch_banded_seeded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
                                            has_fn ? lut.data() : nullptr, dg, band_arg(band), fe, res.data(), ops.data(), cap),
               "sa_align_batch_banded_seeded");
@@ -555,9 +570,10 @@ template <typename Ty, typename ContainerType, typename MatchFnTy, typename SubF
 void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
            const std::vector<std::pair<ContainerType*, ContainerType*>>& pairs, std::vector<sa_result>& res,
            long long band = kNoBand, const SubFnTy* sub = nullptr, long long free_ends = kNoFreeEnds,
-           const std::vector<int32_t>* diags = nullptr) {
+           const std::vector<int32_t>* diags = nullptr, long long xdrop = kNoExtend) {
     const uint32_t fe = free_ends == kNoFreeEnds ? 0 : free_ends_arg(free_ends, band, sub != nullptr);
     const int32_t* dg = diags_arg(diags, pairs.size(), free_ends);
+    const int32_t xd = xdrop == kNoExtend ? 0 : xdrop_arg(xdrop, band, sub != nullptr);
     PhaseTimer tm;
     PackedBatch<Ty> pk;
     pack_batch(pk, pairs);
@@ -587,7 +603,11 @@ void score(int algo, const sa_scoring& sc, MatchFnTy& fn, bool has_fn,
         std::vector<uint8_t> lut;
         if (has_fn) lut = build_lut(coder, fn);
         const bool aff = banded_is_affine(algo);
-        if (diags)
+        if (xdrop != kNoExtend)
+            check(sa_score_batch_banded_extend(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
+                                               has_fn ? lut.data() : nullptr, band_arg(band), xd, res.data()),
+                  "sa_score_batch_banded_extend");
+        else if (diags)
             check(sa_score_batch_banded_seeded(context(), algo, &sc, s1.data(), o1.data(), s2.data(), o2.data(), n,
                                                has_fn ? lut.data() : nullptr, dg, band_arg(band), fe, res.data()),
                   "sa_score_batch_banded_seeded");

@@ -62,9 +62,11 @@ enum {
     SA_FLAG_TIMEOUT = 8,      /* internal, never returned: a multi-workgroup (SPLIT) band's
                                  bounded wait for the band above it expired; the same call
                                  re-runs such pairs on the single-workgroup plan         */
-    SA_FLAG_RECOVERED = 16    /* informational: a consistency guard of the band-parallel
+    SA_FLAG_RECOVERED = 16,   /* informational: a consistency guard of the band-parallel
                                  traceback fired and the pair was re-walked serially; the
                                  result is exact                                          */
+    SA_FLAG_DROPPED = 32      /* sa_*_batch_banded_extend: the X-drop rule stopped the pair's
+                                 sweep before the end of its band                         */
 };
 
 /* ScoringSystem (include/SequenceAlignment.h:82-131).  Which fields are meaningful depends on
@@ -547,6 +549,71 @@ int sa_score_batch_banded_seeded(sa_ctx* ctx, int algo, const sa_scoring* scorin
                                  const uint8_t* match_lut, const int32_t* diag, uint32_t band, uint32_t free_ends,
                                  sa_result* results);
 int sa_banded_seeded_plan_query(int algo, uint64_t m, uint64_t n, int32_t diag, uint32_t band, uint32_t free_ends,
+                                int* cells_per_lane, int* pairs_per_wave, uint64_t* ws_bytes_per_pair);
+
+/* Banded X-drop extension: the alignment mode of a seed-and-extend mapper.  The alignment is anchored at
+ * (0, 0), may end at any cell, and a pair's sweep is abandoned once its score has fallen too far below
+ * its best.  A caller extends to the right of a seed by passing the two suffixes after the seed, and to
+ * the left by passing the two reversed prefixes.  band = w and xdrop are the same for every pair.
+ * Algorithms.  SA_NW (SA_HIRSCHBERG means NW): 2-bit records, B' <= 4096.  SA_GLOBAL_GOTOH: 4-bit
+ *   records, B' <= 2048.  SA_SW, SA_LOCAL_GOTOH, SA_MYERS_MILLER: SA_ERR_UNSUPPORTED; an invalid value:
+ *   SA_ERR_ARG.
+ * Band.  That of the seeded calls round diagonal 0: lo' = max(-w, -m), hi' = min(w, n), B' = hi' - lo' + 1
+ *   <= 2w + 1: w diagonals either side of diagonal 0.  The anchor (0, 0) is always inside it, (m, n) need
+ *   not be; there is no legality rule and no diag argument.
+ * Recurrence, borders, tie order, records and op codes.  Those of sa_align_batch_banded_seeded with
+ *   free_ends = 0: borders k * gap (NW), gap_open + k * gap_extend with X = Y = -10000 (GlobalGotoh); a
+ *   term that would read a cell outside the band is no candidate.
+ * End cell.  The candidates are (0, 0), which holds 0, and every in-band interior cell (i >= 1, j >= 1)
+ *   the sweep computed; border cells other than (0, 0) are no candidates.  The end cell is the last
+ *   candidate in row-major order that holds the maximum of H (GlobalGotoh: M) over the candidates; score
+ *   is that value, never negative, and (end_i, end_j) that cell.
+ * Drop rule.  Steps are the band's own: an in-band cell (i, j) belongs to step t = i + j - lo'; the last
+ *   step is tend = min(m + n, 2m + hi', 2n - lo') - lo'.  A checkpoint follows every step t with
+ *   t = SA_XDROP_PERIOD - 1 (mod SA_XDROP_PERIOD) and t < tend.  There, best is the candidates' maximum
+ *   over all steps <= t, and recent the maximum of H (M) over the interior in-band cells of the steps
+ *   t - SA_XDROP_PERIOD + 1 .. t.  If those steps hold at least one interior cell, xdrop >= 0 and
+ *   best - recent > xdrop, the pair stops: it has no cells of later steps, and SA_FLAG_DROPPED is set.
+ *   Nothing is pruned before the stop: every cell of a step <= t has exactly the value the unstopped
+ *   recurrence gives it.  xdrop = SA_XDROP_OFF never stops; xdrop < -1: SA_ERR_ARG.
+ * Walk.  From the end cell (GlobalGotoh: in type 0) to (0, 0) with the banded call's candidate order /
+ *   state machine; at j == 0 'U', at i == 0 'L'.  start = (0, 0); flags is 0 or SA_FLAG_DROPPED.  The ops
+ *   cover Seq1[0, end_i) and Seq2[0, end_j) only.
+ * Score call.  start = (-1, -1), nops = 0, reserved = 0; no records, no walk; score, end cell and
+ *   SA_FLAG_DROPPED exactly as the align call's.
+ * Equivalences.
+ *   (a) For any xdrop, a result with end cell (e_i, e_j) equals sa_align_batch_banded_seeded on the
+ *       prefixes Seq1[0, e_i) and Seq2[0, e_j) with diag = 0, the same band and free_ends = 0, in score,
+ *       end cell, start, nops and every op: the two prefix bands hold the same cells with the same values.
+ *   (b) For fixed inputs the score does not fall as xdrop grows, and equals the SA_XDROP_OFF score from
+ *       some xdrop on.
+ * Status codes (all checked before the context is looked at, so a NULL context gives the same answer; a
+ * NULL context with valid arguments: SA_ERR_ARG):
+ *   an invalid algo; band >= 2^31; xdrop < -1: SA_ERR_ARG.
+ *   As the seeded calls: band == 0 without allow_mismatch, gap_extend > 0 (GlobalGotoh), the 2^29 score
+ *   bound per pair, m or n >= 2^24, B' above 4096 / 2048: SA_ERR_UNSUPPORTED.  (m + 1) * B' >= 2^31:
+ *   SA_ERR_UNSUPPORTED, as for banded SW, whose end-cell key this is.  SA_ERR_CAPACITY; SA_ERR_NOMEM.
+ * Records (align call): sized for tend - tb + 1 steps per pair as in the seeded call, tb = (-lo') & ~1; a
+ *   stopped pair leaves the rest unwritten.  Launch splitting under sa_set_workspace_limit, the joining of
+ *   neighbouring variants ($SEQALIB_BAND_MERGE), sa_last_timings and sa_last_plan_ex (SA_KERNEL_BANDED,
+ *   the widest variant's cells per lane, 1 wave, SA_RECORDS_BAND2 / BAND4 / NONE) work as for the banded
+ *   calls.  The cost of a call depends on its data: a wave leaves the sweep once all its pairs have
+ *   stopped or ended.
+ * sa_banded_extend_plan_query (host-only): variant, pairs per wave and record bytes of one shape, or the
+ *   status the calls give it. */
+#define SA_XDROP_OFF (-1)
+#define SA_XDROP_PERIOD 16
+int sa_align_batch_banded_extend(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const uint8_t* match_lut, uint32_t band, int32_t xdrop,
+                                 sa_result* results, uint8_t* ops, uint64_t ops_cap);
+int sa_score_batch_banded_extend(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                 const uint8_t* seq1, const uint64_t* seq1_off,
+                                 const uint8_t* seq2, const uint64_t* seq2_off, uint32_t npairs,
+                                 const uint8_t* match_lut, uint32_t band, int32_t xdrop,
+                                 sa_result* results);
+int sa_banded_extend_plan_query(int algo, uint64_t m, uint64_t n, uint32_t band,
                                 int* cells_per_lane, int* pairs_per_wave, uint64_t* ws_bytes_per_pair);
 
 /* Device time of the kernels of the last sa_align_batch[_device] call, from HIP events

@@ -34,6 +34,7 @@ __all__ = [
     "load_library", "library_path", "expand_ops", "synth_dna", "synth_mutate", "synth_dna_batch",
     "SA_FLAG_DIVERGED", "SA_FLAG_BAD_SHAPE", "SA_FLAG_SIZE_HACK", "SA_FLAG_TIMEOUT",
     "SA_RECORDS_NONE", "score_plan_query",
+    "SA_FLAG_DROPPED", "SA_XDROP_OFF", "SA_XDROP_PERIOD", "banded_extend_plan_query",
 ]
 
 SA_SW, SA_NW, SA_LOCAL_GOTOH, SA_GLOBAL_GOTOH, SA_HIRSCHBERG, SA_MYERS_MILLER = 0, 1, 2, 3, 4, 5
@@ -49,6 +50,10 @@ SA_RECORDS_BAND2 = 4  # banded align calls: 2 bits per in-band cell, laid out by
 SA_RECORDS_BAND4 = 5  # banded affine align calls: 4 bits per in-band cell
 # free_ends of the ends-free banded calls (sa_align_batch_banded_ends_free): which unaligned heads / tails cost nothing
 SA_FREE_SEQ1_BEGIN, SA_FREE_SEQ1_END, SA_FREE_SEQ2_BEGIN, SA_FREE_SEQ2_END = 1, 2, 4, 8
+# the banded extension calls (sa_align_batch_banded_extend): the flag of a pair the X-drop rule stopped, the
+# xdrop that never stops one, and the steps between two checkpoints
+SA_FLAG_DROPPED = 32
+SA_XDROP_OFF, SA_XDROP_PERIOD = -1, 16
 SA_HOOK_HAND_TAG, SA_HOOK_POISON_WS, SA_HOOK_F16 = 1, 2, 3   # sa_test_hook (tests only)
 INT32_MIN = -(2 ** 31)
 
@@ -169,6 +174,11 @@ def load_library():
                                                C.c_uint32, C.c_uint32, vp]
     L.sa_banded_seeded_plan_query.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32,
                                               i32p, i32p, u64p]
+    L.sa_align_batch_banded_extend.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
+                                               C.c_uint32, C.c_int32, vp, vp, C.c_uint64]
+    L.sa_score_batch_banded_extend.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
+                                               C.c_uint32, C.c_int32, vp]
+    L.sa_banded_extend_plan_query.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, i32p, i32p, u64p]
     L.sa_last_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32p]
     L.sa_last_kernel_timings.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sa_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, i32p, u64p, u64p]
@@ -192,6 +202,7 @@ def load_library():
                "sa_align_batch_banded_matrix", "sa_score_batch_banded_matrix",
                "sa_align_batch_banded_ends_free", "sa_score_batch_banded_ends_free",
                "sa_align_batch_banded_seeded", "sa_score_batch_banded_seeded", "sa_banded_seeded_plan_query",
+               "sa_align_batch_banded_extend", "sa_score_batch_banded_extend", "sa_banded_extend_plan_query",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -366,6 +377,13 @@ def _diag_arg(diag, npairs: int) -> np.ndarray:
     if d.size and (d.min() < -(2 ** 31) or d.max() >= 2 ** 31):
         raise SeqalibError("a seed diagonal does not fit 32 bits")
     return np.ascontiguousarray(d, dtype=np.int32)
+
+
+def _xdrop_arg(xdrop) -> int:
+    xdrop = int(xdrop)
+    if xdrop < -(2 ** 31) or xdrop >= 2 ** 31:
+        raise SeqalibError(f"xdrop does not fit 32 bits: {xdrop}")   # (the library answers a value below SA_XDROP_OFF)
+    return xdrop
 
 
 def _lut_arg(lut) -> Optional[np.ndarray]:
@@ -629,6 +647,36 @@ class Engine:
         """score() through the seeded banded call."""
         s1, off1, s2, off2 = pack_pairs(pairs)
         return self._score_results(self.score_banded_seeded_packed(algo, scoring, s1, off1, s2, off2, diag, band, free_ends, lut))
+
+    def align_banded_extend_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, band: int, xdrop: int,
+                                   lut: Optional[np.ndarray] = None):
+        """Banded X-drop extension host-buffer batch (sa_align_batch_banded_extend): banded NW (SA_NW,
+        SA_HIRSCHBERG) or GlobalGotoh anchored at (0, 0) in the band round diagonal 0, ending at its best
+        cell; a pair whose score falls more than xdrop below its best stops early (SA_FLAG_DROPPED;
+        SA_XDROP_OFF: never).  Returns (results, ops) as align_packed."""
+        return self._banded_call("sa_align_batch_banded_extend", algo, scoring, s1, off1, s2, off2, band, lut,
+                                 (_xdrop_arg(xdrop),))
+
+    def score_banded_extend_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
+                                   s2: np.ndarray, off2: np.ndarray, band: int, xdrop: int,
+                                   lut: Optional[np.ndarray] = None) -> np.ndarray:
+        """Banded extension score batch (sa_score_batch_banded_extend): the results array (start = -1, nops = 0)."""
+        return self._banded_call("sa_score_batch_banded_extend", algo, scoring, s1, off1, s2, off2, band, lut,
+                                 (_xdrop_arg(xdrop),), with_ops=False)
+
+    def align_banded_extend(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                            xdrop: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """align() through the banded extension call."""
+        def call(algo, scoring, s1, off1, s2, off2, band, lut):
+            return self.align_banded_extend_packed(algo, scoring, s1, off1, s2, off2, band, xdrop, lut)
+        return self._align_banded_pairs(call, algo, scoring, pairs, band, lut)
+
+    def score_banded_extend(self, algo: int, scoring: ScoringSystem, pairs: Sequence[Tuple[object, object]], band: int,
+                            xdrop: int, lut: Optional[np.ndarray] = None) -> List[PairResult]:
+        """score() through the banded extension call."""
+        s1, off1, s2, off2 = pack_pairs(pairs)
+        return self._score_results(self.score_banded_extend_packed(algo, scoring, s1, off1, s2, off2, band, xdrop, lut))
 
     def _packed_call(self, fn, algo, scoring, s1, off1, s2, off2, mid, with_ops):
         """One host-buffer batch call of the banded / matrix families.  mid: the entry point's arguments
@@ -970,6 +1018,17 @@ def banded_seeded_plan_query(algo: int, m: int, n: int, diag: int, band: int, fr
     return R.value, ppw.value, ws.value
 
 
+def banded_extend_plan_query(algo: int, m: int, n: int, band: int):
+    """(cells per lane and step, pairs per wave, record bytes) of the banded extension calls for one pair of
+    m x n (sa_banded_extend_plan_query).  Raises where the calls refuse the shape."""
+    L = load_library()
+    R, ppw, ws = C.c_int(), C.c_int(), C.c_uint64()
+    rc = L.sa_banded_extend_plan_query(algo, m, n, _band_arg(band), C.byref(R), C.byref(ppw), C.byref(ws))
+    if rc:
+        raise SeqalibError(f"sa_banded_extend_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
+    return R.value, ppw.value, ws.value
+
+
 def matrix_plan_query(algo: int, scoring: "ScoringSystem", max_m: int, max_n: int, npairs: int, nsym: int = 20):
     """(kernel, R, W, workspace bytes per pair) of sa_align_batch_matrix for a batch of this shape with
     nsym distinct symbols (sa_matrix_plan_query; no GPU needed)."""
@@ -1187,6 +1246,45 @@ class _Aligner:
     def getSeededEndCells(self, pairs: Sequence[Tuple[object, object]], diags, band: int, free_ends: int) -> List[Tuple[int, int]]:
         """(end_i, end_j) of every pair, as getEndsFreeEndCells."""
         return [(r.end_i, r.end_j) for r in self._seeded_score_results(pairs, diags, band, free_ends)]
+
+
+    def _extension_check(self):
+        if self.ALGO not in (SA_NW, SA_HIRSCHBERG, SA_GLOBAL_GOTOH):
+            raise SeqalibError(f"{type(self).__name__} has no extension form: NeedlemanWunschSA, HirschbergSA (= NW) and GlobalGotohSA do")
+        if self.matrix is not None:
+            raise SeqalibError("a substitution matrix and an extension cannot be combined: the banded extension calls take match / mismatch scorings")
+
+    def getExtensionAlignments(self, pairs: Sequence[Tuple[object, object]], band: int, xdrop: int) -> List[AlignedSequence]:
+        """X-drop extensions (sa_align_batch_banded_extend; NeedlemanWunschSA, HirschbergSA = NW,
+        GlobalGotohSA; the other aligners raise SeqalibError): each pair aligned from its first symbols
+        on, inside `band` diagonals either side of the main one, up to the cell of its best score; a pair
+        whose score falls more than xdrop below its best is abandoned there (SA_XDROP_OFF: never).  The
+        aligned prefix comes from the ops; the unextended tails are printed the way forceGlobal prints a
+        local alignment's."""
+        self._extension_check()
+        res = _engine(self.device).align_banded_extend(self.ALGO, self.scoring, pairs, band, xdrop, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return [expand_ops(SA_SW, a, b, r, self.blank) for (a, b), r in zip(pairs, res)]   # (SA_SW: forceGlobal over (start, end))
+
+    def getExtensionAlignment(self, seq1, seq2, band: int, xdrop: int) -> AlignedSequence:
+        return self.getExtensionAlignments([(seq1, seq2)], band, xdrop)[0]
+
+    def _extension_score_results(self, pairs, band: int, xdrop: int) -> List[PairResult]:
+        self._extension_check()
+        res = _engine(self.device).score_banded_extend(self.ALGO, self.scoring, pairs, band, xdrop, self._lut(pairs))
+        self.last = res[-1] if res else None
+        return res
+
+    def getExtensionScores(self, pairs: Sequence[Tuple[object, object]], band: int, xdrop: int) -> List[int]:
+        return [r.score for r in self._extension_score_results(pairs, band, xdrop)]
+
+    def getExtensionEndCells(self, pairs: Sequence[Tuple[object, object]], band: int, xdrop: int) -> List[Tuple[int, int]]:
+        """(end_i, end_j) of every pair: the last row-major cell holding the extension's maximum, (0, 0) if none is positive."""
+        return [(r.end_i, r.end_j) for r in self._extension_score_results(pairs, band, xdrop)]
+
+    def getExtensionDropped(self, pairs: Sequence[Tuple[object, object]], band: int, xdrop: int) -> List[bool]:
+        """Whether the X-drop rule stopped each pair (SA_FLAG_DROPPED)."""
+        return [bool(r.flags & SA_FLAG_DROPPED) for r in self._extension_score_results(pairs, band, xdrop)]
 
 
 class _LocalAligner(_Aligner):

@@ -5,7 +5,8 @@
 // Every pair gets the fill variant (cells per lane R, lanes per pair L) its clipped band fits; the pairs of
 // one variant are launched together, longest first, in as many launches as sa_set_workspace_limit leaves
 // room for their records.  A score call stores no records and launches no walk.  The linear, affine,
-// matrix, ends-free and seeded calls differ in their checks, variant list, record size and launchers only.
+// matrix, ends-free, seeded and extension calls differ in their checks, variant list, record size and
+// launchers only.
 #include <stdlib.h>
 
 #include "sa_api_ctx.h"
@@ -44,6 +45,10 @@ struct BandCall {
     // round its seed diagonal, which travels behind each launch's idx entries.  diag may be NULL when npairs is 0
     bool seeded = false;
     const int32_t* diag = nullptr;
+    // the extension calls: the seeded band round diagonal 0 for every pair (no diagonals travel), NW's or
+    // GlobalGotoh's borders, and xdrop for their fills
+    bool extend = false;
+    int32_t xdrop = SA_XDROP_OFF;
 };
 
 constexpr CallRules kLinearRules = {
@@ -65,10 +70,15 @@ constexpr CallRules kSeededRules = {
     .algos = kAlgoGlobal,
     .unsupported = "seeded banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only",
     .free_ends = true, .band_early = "band: 2 * band + 1 diagonals overflow 32 bits"};
+constexpr CallRules kExtendRules = {
+    .algos = kAlgoGlobal,
+    .unsupported = "banded extension calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only",
+    .band_early = "band: 2 * band + 1 diagonals overflow 32 bits"};
 
 // What the launch loop and the plan read of a call's family, fixed for the whole call.  The launchers
 // (sa_internal.h) differ in their signatures; fill and walk adapt them: the ends-free and seeded ones take
-// no algorithm and only kMatchEq / kMatchLut, the linear ones the BandParams base of the block.
+// no algorithm and only kMatchEq / kMatchLut, as the extension ones; the linear ones the BandParams base of
+// the block.
 using BandFill = hipError_t (*)(int algo, int v, int mm, bool rec, const BandAffineParams& p, hipStream_t s);
 using BandWalk = hipError_t (*)(int algo, bool lut, const BandAffineParams& p, hipStream_t s);
 struct BandFamily {
@@ -84,7 +94,7 @@ constexpr BandFamily linear_family(BandFill fill, BandWalk walk) {
 constexpr BandFamily affine_family(BandFill fill, BandWalk walk) {
     return {fill, walk, band_affine_rec_words, kBandAffineVariants, SA_RECORDS_BAND4};
 }
-const BandFamily kBandFamilies[3][2] = {   // [corridor, ends-free, seeded][linear, affine]
+const BandFamily kBandFamilies[4][2] = {   // [corridor, ends-free, seeded, extension][linear, affine]
     {linear_family([](int algo, int v, int mm, bool rec, const BandAffineParams& p, hipStream_t s) { return launch_banded_fill(algo, v, mm, rec, p, s); },
                    [](int algo, bool lut, const BandAffineParams& p, hipStream_t s) { return launch_banded_tb(algo, lut, p, s); }),
      affine_family([](int algo, int v, int mm, bool rec, const BandAffineParams& p, hipStream_t s) { return launch_banded_affine_fill(algo, v, mm, rec, p, s); },
@@ -97,9 +107,13 @@ const BandFamily kBandFamilies[3][2] = {   // [corridor, ends-free, seeded][line
                    [](int algo, bool lut, const BandAffineParams& p, hipStream_t s) { return launch_banded_seeded_tb(lut, p, s); }),
      affine_family([](int algo, int v, int mm, bool rec, const BandAffineParams& p, hipStream_t s) { return launch_banded_affine_seeded_fill(v, mm == kMatchLut, rec, p, s); },
                    [](int algo, bool lut, const BandAffineParams& p, hipStream_t s) { return launch_banded_affine_seeded_tb(lut, p, s); })},
+    {linear_family([](int algo, int v, int mm, bool rec, const BandAffineParams& p, hipStream_t s) { return launch_banded_extend_fill(v, mm == kMatchLut, rec, p, s); },
+                   [](int algo, bool lut, const BandAffineParams& p, hipStream_t s) { return launch_banded_extend_tb(lut, p, s); }),
+     affine_family([](int algo, int v, int mm, bool rec, const BandAffineParams& p, hipStream_t s) { return launch_banded_affine_extend_fill(v, mm == kMatchLut, rec, p, s); },
+                   [](int algo, bool lut, const BandAffineParams& p, hipStream_t s) { return launch_banded_affine_extend_tb(lut, p, s); })},
 };
-const BandFamily& band_family(bool seeded, bool ends_free, bool affine) {
-    return kBandFamilies[seeded ? 2 : ends_free ? 1 : 0][affine];
+const BandFamily& band_family(bool extend, bool seeded, bool ends_free, bool affine) {
+    return kBandFamilies[extend ? 3 : seeded ? 2 : ends_free ? 1 : 0][affine];
 }
 
 // ------------------------------------------------------------------------------ per-pair limits
@@ -108,6 +122,7 @@ struct BandSeed {
     int32_t diag;        // the seed diagonal, -m <= diag <= n (checked by the caller)
     uint32_t free_ends;
     uint64_t pair;       // for the message
+    bool extend = false; // the extension calls: diag 0, no legality rule (the anchor (0, 0) is in every band), SW's key limit
 };
 
 // The seeded legality rule: the band must hold a legal begin and a legal end (include/seqalib_hip.h).
@@ -158,6 +173,10 @@ int banded_pair_plan(sa_ctx* c, int algo, const sa_scoring* sc, uint64_t m, uint
     if ((algo == SA_SW || algo == SA_LOCAL_GOTOH) && (m + 1) * (uint64_t)g->beff >= (1ull << 31))
         return fail(c, SA_ERR_UNSUPPORTED, affine ? "banded LocalGotoh needs (m + 1) * band diagonals < 2^31"
                                                   : "banded SW needs (m + 1) * band diagonals < 2^31");
+    if (seed && seed->extend)
+        return (m + 1) * (uint64_t)g->beff >= (1ull << 31)
+                   ? fail(c, SA_ERR_UNSUPPORTED, "banded extension needs (m + 1) * band diagonals < 2^31")
+                   : SA_OK;
     return seed ? banded_seed_legal(c, *seed, *g, (int64_t)m, (int64_t)n) : SA_OK;
 }
 
@@ -168,11 +187,11 @@ int band_algo(int algo) { return algo == SA_HIRSCHBERG ? SA_NW : algo; }
 int banded_pair_limits(sa_ctx* c, const BandCall& k) {
     for (uint32_t p = 0; p < k.npairs; ++p) {
         if (k.off1[p + 1] < k.off1[p] || k.off2[p + 1] < k.off2[p]) return fail(c, SA_ERR_ARG, "offsets must be non-decreasing");
-        const BandSeed sd{k.seeded ? k.diag[p] : 0, k.free_ends, p};
+        const BandSeed sd{k.seeded ? k.diag[p] : 0, k.free_ends, p, k.extend};
         BandGeom g;
         int v = 0;
         if (int rc = banded_pair_plan(c, band_algo(k.algo), k.sc, k.off1[p + 1] - k.off1[p], k.off2[p + 1] - k.off2[p], k.band,
-                                      &g, &v, k.seeded ? &sd : nullptr))
+                                      &g, &v, k.seeded || k.extend ? &sd : nullptr))
             return rc;
     }
     return SA_OK;
@@ -181,7 +200,7 @@ int banded_pair_limits(sa_ctx* c, const BandCall& k) {
 // ------------------------------------------------------------------------------------ phases
 // The linear corridor calls leave their per-pair limits to the context (banded_plan); every other
 // family's answer without one as well.
-bool early_limits(const BandCall& k) { return k.affine || k.sub || k.ends_free; }
+bool early_limits(const BandCall& k) { return k.affine || k.sub || k.ends_free || k.extend; }
 
 // The checks that need no context, so they answer without a device too.
 int banded_checks(sa_ctx* c, const BandCall& k) {
@@ -203,7 +222,8 @@ int banded_buffers(sa_ctx* c, const BandCall& k, uint64_t* ops_total) {
 int banded_plan(sa_ctx* c, const BandCall& k, const BandFamily& fam, BandGroups* grp) {
     if (!early_limits(k))
         if (int rc = banded_pair_limits(c, k)) return rc;
-    BandGroupIn in{k.off1, k.off2, k.npairs, k.seeded ? k.diag : nullptr, (int32_t)std::min(k.band, kBandMaxW),
+    const std::vector<int32_t> zero_diag(k.extend ? k.npairs : 0, 0);   // the extension band: every pair round diagonal 0
+    BandGroupIn in{k.off1, k.off2, k.npairs, k.extend ? zero_diag.data() : k.seeded ? k.diag : nullptr, (int32_t)std::min(k.band, kBandMaxW),
                    fam.nvariants, fam.rec_words, k.notb, 0, 0, true};
     in.budget_words = k.notb ? 0 : ws_budget(c) / 4;
     const char* merge_env = getenv("SEQALIB_BAND_MERGE");
@@ -350,7 +370,7 @@ int banded_launch(sa_ctx* c, const BandCall& k, const BandFamily& fam, const Ban
         bp.L = kBandL[ln.v];
         bp.submat = k.sub ? d.dtab : nullptr;
         bp.sub_k = k.sub ? (uint32_t)k.sub->K : 0;
-        bp.free_ends = k.free_ends;
+        bp.free_ends = k.extend ? (uint32_t)k.xdrop : k.free_ends;
         bp.gap_open = sc->gap_open;
         bp.gap_extend = sc->gap_extend;
         SA_HIP(c, hipEventRecord(ev[0], st));
@@ -401,7 +421,7 @@ int banded_batch(sa_ctx* c, const BandCall& k) {
     if (!k.npairs) return SA_OK;
     SA_HIP(c, hipSetDevice(c->device));
     if ((rc = order_after_last(c, c->stream))) return rc;
-    const BandFamily& fam = band_family(k.seeded, k.ends_free, k.affine);
+    const BandFamily& fam = band_family(k.extend, k.seeded, k.ends_free, k.affine);
     BandGroups grp;
     if ((rc = banded_plan(c, k, fam, &grp))) return rc;
     BandDevice dev;
@@ -457,6 +477,18 @@ int banded_seeded_batch(sa_ctx* c, BandCall k, const int32_t* diag, uint32_t fre
     return banded_batch(c, k);
 }
 
+// The extension calls: their own checks, then banded_batch with the band round diagonal 0, whose per-pair
+// limits apply SW's key limit in place of the legality rule.
+int banded_extend_batch(sa_ctx* c, BandCall k, int32_t xdrop) {
+    if (xdrop < SA_XDROP_OFF) return fail(c, SA_ERR_ARG, "xdrop must be SA_XDROP_OFF or >= 0");
+    if (int rc = check_call(c, kExtendRules, k.algo, k.sc, k.band, 0)) return rc;
+    k.affine = k.algo == SA_GLOBAL_GOTOH;
+    k.rules = k.affine ? &kAffineRules : &kLinearRules;
+    k.extend = true;
+    k.xdrop = xdrop;
+    return banded_batch(c, k);
+}
+
 // The symbol scan, codes and dense table of the matrix calls (sub_recode), then banded_batch (linear or
 // affine by algorithm) with the kMatchSub fills.  The per-pair score bounds are the banded calls' own,
 // with the table's extremes in place of match / mismatch -- for the affine algorithms the stricter
@@ -486,7 +518,7 @@ int banded_plan_answer(int algo, bool affine, uint64_t m, uint64_t n, uint32_t b
     if (int rc = banded_pair_plan(nullptr, algo, &kAnyScoring, m, n, band, &g, &v, seed)) return rc;
     if (cells_per_lane) *cells_per_lane = kBandR[v];
     if (pairs_per_wave) *pairs_per_wave = kWave / kBandL[v];
-    if (ws_bytes_per_pair) *ws_bytes_per_pair = band_family(false, false, affine).rec_words(g, v) * 4;
+    if (ws_bytes_per_pair) *ws_bytes_per_pair = band_family(false, false, false, affine).rec_words(g, v) * 4;
     return SA_OK;
 }
 
@@ -573,6 +605,26 @@ int sa_banded_seeded_plan_query(int algo, uint64_t m, uint64_t n, int32_t diag, 
     if (m >= (1u << 24) || n >= (1u << 24)) return fail(nullptr, SA_ERR_UNSUPPORTED, "sequence length >= 2^24");
     if ((rc = banded_seed_in_matrix(nullptr, 0, m, n, diag))) return rc;
     const BandSeed sd{diag, free_ends, 0};
+    return banded_plan_answer(band_algo(algo), algo == SA_GLOBAL_GOTOH, m, n, band, &sd, cells_per_lane, pairs_per_wave,
+                              ws_bytes_per_pair);
+}
+
+int sa_align_batch_banded_extend(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1, const
+                                 uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* match_lut, uint32_t band,
+                                 int32_t xdrop, sa_result* results, uint8_t* ops, uint64_t ops_cap) {
+    const BandCall k = align_call(algo, sc, seq1, off1, seq2, off2, npairs, match_lut, band, results, ops, ops_cap);
+    return banded_extend_batch(c, k, xdrop);
+}
+int sa_score_batch_banded_extend(sa_ctx* c, int algo, const sa_scoring* sc, const uint8_t* seq1, const uint64_t* off1, const
+                                 uint8_t* seq2, const uint64_t* off2, uint32_t npairs, const uint8_t* match_lut, uint32_t band,
+                                 int32_t xdrop, sa_result* results) {
+    return banded_extend_batch(c, score_call(algo, sc, seq1, off1, seq2, off2, npairs, match_lut, band, results), xdrop);
+}
+
+int sa_banded_extend_plan_query(int algo, uint64_t m, uint64_t n, uint32_t band, int* cells_per_lane, int* pairs_per_wave,
+                                uint64_t* ws_bytes_per_pair) {
+    if (int rc = check_call(nullptr, kExtendRules, algo, &kAnyScoring, band, 0)) return rc;
+    const BandSeed sd{0, 0, 0, true};
     return banded_plan_answer(band_algo(algo), algo == SA_GLOBAL_GOTOH, m, n, band, &sd, cells_per_lane, pairs_per_wave,
                               ws_bytes_per_pair);
 }

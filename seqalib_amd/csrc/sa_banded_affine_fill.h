@@ -32,6 +32,11 @@
 //
 // Seeded mode (kMatchSeedBit beside kMatchFreeBit; the sa_*_batch_banded_seeded calls, instantiated by
 // sa_banded_affine_seeded.hip): the ends-free mode with band_geom_seeded, as in sa_banded_fill.h.
+//
+// Extension mode (kMatchExtBit alone; the sa_*_batch_banded_extend calls, instantiated by
+// sa_banded_affine_extend.hip): GlobalGotoh's cell and borders in the band band_geom_seeded(m, n, w, 0),
+// the local mode's running `best` over M of the interior cells, from the key of (0, 0) on, and the X-drop
+// test with its wave-uniform early exit, all as sa_banded_fill.h describes them.
 #pragma once
 #include "sa_internal.h"
 
@@ -41,6 +46,7 @@ namespace {
 constexpr int32_t kBorderXY = -10000;   // X and Y of every border cell (the reference's constant)
 constexpr int kMatchFreeBit = 8;        // in the fill kernel's match-mode template value: the ends-free mode
 constexpr int kMatchSeedBit = 16;       // with kMatchFreeBit: the seeded band (band_geom_seeded, diagonals behind idx)
+constexpr int kMatchExtBit = 32;        // alone: the extension mode (xdrop in BandParams::free_ends)
 
 __device__ __forceinline__ int32_t aff_from_lower_lane(int32_t v) {   // lane l takes lane l - 1's, lane 0 kBandNeg
     return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x138, 0xf, 0xf, false);
@@ -49,9 +55,10 @@ __device__ __forceinline__ int32_t aff_from_upper_lane(int32_t v) {   // lane l 
     return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x130, 0xf, 0xf, false);
 }
 
-template <bool LOCAL, int R, int L, int MM, bool REC, bool FREE>
+template <bool LOCAL, int R, int L, int MM, bool REC, bool FREE, bool EXT = false>
 struct BandAffineFill {
     static_assert(!(LOCAL && FREE), "the ends-free mode is GlobalGotoh's");
+    static_assert(!(EXT && (LOCAL || FREE)), "the extension mode is GlobalGotoh's, with its own end cell");
     static constexpr int S = R <= 8 ? 8 / R : 1;         // steps per record word
     static constexpr int WPS = R <= 8 ? 1 : R / 8;       // record words per step
     int32_t EM[R], EX[R], EY[R], OM[R], OX[R], OY[R];
@@ -65,6 +72,8 @@ struct BandAffineFill {
     int32_t imin, jmin;  // ends-free: candidates are (i, n) with i >= imin and (m, j) with j >= jmin
     int32_t score;       // global: M[m][n]
     uint32_t w[WPS];     // the step's 4-bit records
+    int32_t wmax;        // extension: the maximum of M over the lane's interior cells since the last checkpoint
+    bool dropped;        // extension: the X-drop rule has stopped the pair
 
     // One step.  PAR: 0 even (E), 1 odd (O).  EDGE: the step may hold border cells or cells outside
     // the matrix; otherwise every cell with c < B' is an interior cell.
@@ -136,17 +145,18 @@ struct BandAffineFill {
                 vM = interior ? hv : border ? bval : out;
                 vX = interior ? x : border ? kBorderXY : kBandNeg;
                 vY = interior ? y : border ? kBorderXY : kBandNeg;
-                if (!LOCAL && !FREE && inb && i == m && j == n) score = vM;
+                if (!LOCAL && !FREE && !EXT && inb && i == m && j == n) score = vM;
             } else {
                 vM = inb ? hv : kBandNeg;
                 vX = inb ? x : kBandNeg;
                 vY = inb ? y : kBandNeg;
             }
-            if (LOCAL) {
+            if (LOCAL || EXT) {
                 const long long key = (long long)(((unsigned long long)(uint32_t)hv << 32) | pos);
                 if (interior && key > best) best = key;
                 pos += dpos;
             }
+            if (EXT) wmax = interior ? max(wmax, hv) : wmax;
             if (PAR == 0) {
                 EM[r] = vM;
                 EX[r] = vX;
@@ -174,12 +184,12 @@ struct BandAffineFill {
     }
 };
 
-template <bool LOCAL, int R, int L, int MMF, bool REC>   // MMF: the match mode [| kMatchFreeBit [| kMatchSeedBit]]
+template <bool LOCAL, int R, int L, int MMF, bool REC>   // MMF: the match mode [| kMatchFreeBit [| kMatchSeedBit] | kMatchExtBit]
 __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams P) {
-    constexpr int MM = MMF & ~(kMatchFreeBit | kMatchSeedBit);
-    constexpr bool FREE = (MMF & kMatchFreeBit) != 0, SEEDED = (MMF & kMatchSeedBit) != 0;
+    constexpr int MM = MMF & ~(kMatchFreeBit | kMatchSeedBit | kMatchExtBit);
+    constexpr bool FREE = (MMF & kMatchFreeBit) != 0, SEEDED = (MMF & kMatchSeedBit) != 0, EXT = (MMF & kMatchExtBit) != 0;
     static_assert(FREE || !SEEDED, "the seeded band is an ends-free one");
-    using F = BandAffineFill<LOCAL, R, L, MM, REC, FREE>;
+    using F = BandAffineFill<LOCAL, R, L, MM, REC, FREE, EXT>;
     constexpr int PPW = 64 / L, S = F::S, WPS = F::WPS;
     __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
     if (MM == kMatchLut) {
@@ -212,6 +222,7 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
         s1 += a1;
         s2 += a2;
         bg = SEEDED ? band_geom_seeded(f.m, f.n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+             : EXT  ? band_geom_seeded(f.m, f.n, (int32_t)P.band, 0)
                     : band_geom(f.m, f.n, (int32_t)P.band);
     }
     f.lo = bg.lo;
@@ -226,6 +237,10 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
     f.lut = lut_s;
     f.sub = reinterpret_cast<const int16_t*>(lut_s);
     f.best = FREE ? LLONG_MIN : (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
+    if (EXT) f.best = (long long)(uint32_t)(-bg.lo);   // the key of (0, 0): M = 0 on diagonal c = -lo'
+    if (EXT) f.wmax = kBandNeg;
+    const int32_t xdrop = EXT ? (int32_t)P.free_ends : SA_XDROP_OFF;
+    if (EXT) f.dropped = false;
     f.score = INT_MIN;
     const uint32_t fe = FREE ? P.free_ends : 0u;
     f.z_row0 = (fe & kFreeSeq2Begin) != 0;
@@ -256,7 +271,8 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
         return (uint32_t)x < (uint32_t)f.m ? s1[x] : 0u;
     };
     auto sym2 = [&](int32_t x) -> uint32_t { return (uint32_t)x < (uint32_t)f.n ? s2[x] : 0u; };
-    const int32_t h0 = t0 >> 1, h1 = t1 >> 1;
+    const int32_t h0 = t0 >> 1;
+    int32_t h1 = t1 >> 1;   // (extension: falls when pairs stop)
     const int32_t ab = -f.l * R - 1, bb = f.l * R + f.lo - 1;   // A[r] = Seq1[h + ab - r], Bw[r] = Seq2[h + bb + r]
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -273,6 +289,7 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
         if (!REC) return;
         const int32_t tp = t - bg.tb;
         if (tp < 0 || t > bg.tend) return;
+        if (EXT && f.dropped) return;
         if (R <= 8) {
             const int32_t s = tp % S;
             acc |= f.w[0] << (s * 4 * R);
@@ -316,6 +333,27 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
                 f.template step<1, true>(h);
                 store(t + 1);
             }
+            if (EXT && (t & (SA_XDROP_PERIOD - 1)) == SA_XDROP_PERIOD - 2) {   // a checkpoint follows step t + 1
+                int32_t bs = (int32_t)(f.best >> 32), recent = f.wmax;
+                for (int off = L / 2; off >= 1; off >>= 1) {
+                    bs = max(bs, __shfl_xor(bs, off));
+                    recent = max(recent, __shfl_xor(recent, off));
+                }
+                f.wmax = kBandNeg;
+                // (recent == kBandNeg: the window held no interior cell; bs - recent < 2^30 otherwise)
+                const bool stop = !f.dropped && t + 1 < bg.tend && xdrop >= 0 && recent > kBandNeg && bs - recent > xdrop;
+                if (__any(stop)) {
+                    if (stop) {
+                        const int32_t tp = t + 1 - bg.tb;   // (>= 0: the window held a cell of this pair)
+                        if (REC && R <= 8 && tp % S != S - 1) rec[(uint64_t)(tp / S) * L + f.l] = acc;   // the open record word
+                        f.dropped = true;
+                        f.rlimE = f.rlimO = 0;
+                    }
+                    int32_t te = f.dropped ? -1 : bg.tend;
+                    for (int off = 32; off >= 1; off >>= 1) te = max(te, __shfl_xor(te, off));
+                    h1 = __builtin_amdgcn_readfirstlane(te) >> 1;
+                }
+            }
 #pragma unroll
             for (int r = R - 1; r > 0; --r) f.A[r] = f.A[r - 1];
             f.A[0] = ca[u];
@@ -332,7 +370,18 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
 
     // fold the pair's lanes
     int32_t sc_i = 0, sc_j = 0, sc = f.score;
-    if (FREE) {   // (m, n) is a candidate of every pair, so b is a cell's key
+    if (EXT) {   // best is a candidate's key: (0, 0)'s or an interior cell's
+        long long b = f.best;
+        for (int off = L / 2; off >= 1; off >>= 1) {
+            const long long o = __shfl_xor(b, off);
+            b = o > b ? o : b;
+        }
+        sc = (int32_t)(b >> 32);
+        const uint32_t pos = (uint32_t)b;
+        // (an idle lane group has beff = 0: the division does not trap, and only live pairs are written below)
+        sc_i = (int32_t)(pos / (uint32_t)f.beff);
+        sc_j = sc_i + f.lo + (int32_t)(pos % (uint32_t)f.beff);
+    } else if (FREE) {   // (m, n) is a candidate of every pair, so b is a cell's key
         f.end_cell();
         long long b = f.best;
         for (int off = L / 2; off >= 1; off >>= 1) {
@@ -374,6 +423,7 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
             r->flags = 0;
             r->reserved = 0;
         }
+        if (EXT) r->flags = f.dropped ? SA_FLAG_DROPPED : 0;   // (the walk keeps it)
     }
 }
 

@@ -54,6 +54,18 @@
 // earlier) hold cells with i < 0 or j < 0 only, which stay kBandNeg.  (m, n) is a candidate only when
 // n - m is in the band, which `j >= jmin` / `i >= imin` say already.  The host admits a pair only if a
 // legal begin and a candidate exist, so `best` leaves LLONG_MIN.
+//
+// Extension mode (ALG = kBandAlgExtend, the sa_*_batch_banded_extend calls; instantiated by
+// sa_banded_extend.hip): NW's cell and borders in the band band_geom_seeded(m, n, w, 0), with SW's running
+// `best` over the interior cells, which starts at the key of (0, 0) -- a candidate that holds 0 and
+// precedes every interior cell in row-major order -- and the X-drop test.  t = 2h + PAR is a pair's own
+// step number and the same for every pair of the wave, so the checkpoints (after every step t = 15 mod
+// SA_XDROP_PERIOD) are wave-uniform: each lane keeps `wmax`, the maximum of its interior cells since the
+// last checkpoint, and the pair's L lanes fold it and best's score there.  A pair that stops sets
+// rlimE = rlimO = 0: every later cell of it is kBandNeg and no candidate, and it stores no record.  The
+// sweep's last iteration h1 is then taken again over the pairs still running, so a wave whose pairs
+// have all stopped leaves the loop at once; the exit is wave-uniform and nothing waits.  xdrop (the same
+// for every pair) travels in BandParams::free_ends, which no other part of this mode reads.
 #pragma once
 #include "sa_internal.h"
 
@@ -70,6 +82,7 @@ __device__ __forceinline__ int32_t from_upper_lane(int32_t v) {   // lane l take
 template <int ALG, int R, int L, int MM, bool REC>
 struct BandFill {
     static constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded;
+    static constexpr bool EXT = ALG == kBandAlgExtend;   // NW's cell and borders throughout
     static constexpr int S = R <= 16 ? 16 / R : 1;   // steps per record word
     int32_t E[R], O[R];
     uint32_t A[R], Bw[R + 1];
@@ -82,6 +95,8 @@ struct BandFill {
     int32_t imin, jmin;       // ends-free: candidates are (i, n) with i >= imin and (m, j) with j >= jmin
     int32_t score;       // NW: H[m][n]
     uint32_t w0, w1;     // the step's 2-bit codes (w1: cells 16..31 of R = 32)
+    int32_t wmax;        // extension: the maximum of the lane's interior cells since the last checkpoint
+    bool dropped;        // extension: the X-drop rule has stopped the pair
 
     // One step.  PAR: 0 even (E), 1 odd (O).  EDGE: the step may hold border cells or cells outside
     // the matrix; otherwise every cell with c < B' is an interior cell.
@@ -138,7 +153,7 @@ struct BandFill {
                 interior = inb && (uint32_t)(i - 1) < (uint32_t)m && (uint32_t)(j - 1) < (uint32_t)n;
                 const bool border = inb && ((i == 0 && (uint32_t)j <= (uint32_t)n) || (j == 0 && (uint32_t)i <= (uint32_t)m));
                 const int32_t bval = FREE           ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)(i == 0 ? g_row0 : g_col0))
-                                     : ALG == SA_NW ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)G)
+                                     : ALG == SA_NW || EXT ? (int32_t)((uint32_t)(i == 0 ? j : i) * (uint32_t)G)
                                                     : 0;
                 // (ends-free: a cell past the end of its diagonal keeps the diagonal's last value)
                 const int32_t out = FREE && inb && (i > m || j > n) ? dg : kBandNeg;
@@ -147,11 +162,12 @@ struct BandFill {
             } else {
                 val = inb ? hv : kBandNeg;
             }
-            if (ALG == SA_SW) {
+            if (ALG == SA_SW || EXT) {
                 const long long key = (long long)(((unsigned long long)(uint32_t)hv << 32) | pos);
                 if (interior && key > best) best = key;
                 pos += dpos;
             }
+            if (EXT) wmax = interior ? max(wmax, hv) : wmax;
             if (PAR == 0) E[r] = val;
             else O[r] = val;
             if (REC) {
@@ -209,8 +225,9 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         f.n = (int32_t)(P.off2[pair + 1] - a2);
         s1 += a1;
         s2 += a2;
-        bg = ALG == kBandAlgSeeded ? band_geom_seeded(f.m, f.n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
-                                   : band_geom(f.m, f.n, (int32_t)P.band);
+        bg = ALG == kBandAlgSeeded   ? band_geom_seeded(f.m, f.n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+             : ALG == kBandAlgExtend ? band_geom_seeded(f.m, f.n, (int32_t)P.band, 0)
+                                     : band_geom(f.m, f.n, (int32_t)P.band);
     }
     f.lo = bg.lo;
     f.beff = bg.beff;
@@ -222,6 +239,10 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
     f.lut = lut_s;
     f.sub = reinterpret_cast<const int16_t*>(lut_s);
     f.best = F::FREE ? LLONG_MIN : (long long)(((unsigned long long)(uint32_t)kBandNeg) << 32);
+    if (F::EXT) f.best = (long long)(uint32_t)(-bg.lo);   // the key of (0, 0): H = 0 on diagonal c = -lo'
+    if (F::EXT) f.wmax = kBandNeg;
+    const int32_t xdrop = F::EXT ? (int32_t)P.free_ends : SA_XDROP_OFF;
+    if (F::EXT) f.dropped = false;
     f.score = INT_MIN;
     const uint32_t fe = F::FREE ? P.free_ends : 0u;
     f.g_row0 = (fe & kFreeSeq2Begin) ? 0 : P.gap;
@@ -252,7 +273,8 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         return (uint32_t)x < (uint32_t)f.m ? s1[x] : 0u;
     };
     auto sym2 = [&](int32_t x) -> uint32_t { return (uint32_t)x < (uint32_t)f.n ? s2[x] : 0u; };
-    const int32_t h0 = t0 >> 1, h1 = t1 >> 1;
+    const int32_t h0 = t0 >> 1;
+    int32_t h1 = t1 >> 1;   // (extension: falls when pairs stop)
     const int32_t ab = -f.l * R - 1, bb = f.l * R + f.lo - 1;   // A[r] = Seq1[h + ab - r], Bw[r] = Seq2[h + bb + r]
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -269,6 +291,7 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         if (!REC) return;
         const int32_t tp = t - bg.tb;
         if (tp < 0 || t > bg.tend) return;
+        if (F::EXT && f.dropped) return;
         if (R <= 16) {
             const int32_t s = tp % S;
             acc |= f.w0 << (s * 2 * R);
@@ -313,6 +336,27 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
                 f.template step<1, true>(h);
                 store(t + 1);
             }
+            if (F::EXT && (t & (SA_XDROP_PERIOD - 1)) == SA_XDROP_PERIOD - 2) {   // a checkpoint follows step t + 1
+                int32_t bs = (int32_t)(f.best >> 32), recent = f.wmax;
+                for (int off = L / 2; off >= 1; off >>= 1) {
+                    bs = max(bs, __shfl_xor(bs, off));
+                    recent = max(recent, __shfl_xor(recent, off));
+                }
+                f.wmax = kBandNeg;
+                // (recent == kBandNeg: the window held no interior cell; bs - recent < 2^30 otherwise)
+                const bool stop = !f.dropped && t + 1 < bg.tend && xdrop >= 0 && recent > kBandNeg && bs - recent > xdrop;
+                if (__any(stop)) {
+                    if (stop) {
+                        const int32_t tp = t + 1 - bg.tb;   // (>= 0: the window held a cell of this pair)
+                        if (REC && R <= 16 && tp % S != S - 1) rec[(uint64_t)(tp / S) * L + f.l] = acc;   // the open record word
+                        f.dropped = true;
+                        f.rlimE = f.rlimO = 0;
+                    }
+                    int32_t te = f.dropped ? -1 : bg.tend;
+                    for (int off = 32; off >= 1; off >>= 1) te = max(te, __shfl_xor(te, off));
+                    h1 = __builtin_amdgcn_readfirstlane(te) >> 1;
+                }
+            }
 #pragma unroll
             for (int r = R - 1; r > 0; --r) f.A[r] = f.A[r - 1];
             f.A[0] = ca[u];
@@ -333,6 +377,17 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
         for (int off = L / 2; off >= 1; off >>= 1) sc = max(sc, __shfl_xor(sc, off));
         sc_i = f.m;
         sc_j = f.n;
+    } else if (F::EXT) {   // best is a candidate's key: (0, 0)'s or an interior cell's
+        long long b = f.best;
+        for (int off = L / 2; off >= 1; off >>= 1) {
+            const long long o = __shfl_xor(b, off);
+            b = o > b ? o : b;
+        }
+        sc = (int32_t)(b >> 32);
+        const uint32_t pos = (uint32_t)b;
+        // (an idle lane group has beff = 0: the division does not trap, and only live pairs are written below)
+        sc_i = (int32_t)(pos / (uint32_t)f.beff);
+        sc_j = sc_i + f.lo + (int32_t)(pos % (uint32_t)f.beff);
     } else if (F::FREE) {   // (m, n) is a candidate of every pair (seeded: the host admits a pair with a candidate only), so b is a cell's key
         f.end_cell();
         long long b = f.best;
@@ -371,6 +426,7 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
             r->flags = 0;
             r->reserved = 0;
         }
+        if (F::EXT) r->flags = f.dropped ? SA_FLAG_DROPPED : 0;   // (the walk keeps it)
     }
 }
 
@@ -399,7 +455,8 @@ hipError_t launch_band_fill_alg(int variant, bool rec, const BandParams& p, hipS
 }
 
 // The walk: one lane per pair over the 2-bit records (0 stop, 1 diagonal, 2 up, 3 left).  Ends-free
-// (kBandAlgFree): it starts at the fill's end cell and stops at a border whose begin is free.
+// (kBandAlgFree): it starts at the fill's end cell and stops at a border whose begin is free.  Extension
+// (kBandAlgExtend): it starts at the fill's end cell too, walks to (0, 0) and keeps the fill's flag.
 template <int ALG, bool LUT>
 __global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
     constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded;
@@ -410,8 +467,9 @@ __global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
     const int32_t m = (int32_t)(P.off1[pair + 1] - a1), n = (int32_t)(P.off2[pair + 1] - a2);
     const uint8_t* s1 = P.seq1 + a1;
     const uint8_t* s2 = P.seq2 + a2;
-    const BandGeom bg = ALG == kBandAlgSeeded ? band_geom_seeded(m, n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
-                                              : band_geom(m, n, (int32_t)P.band);
+    const BandGeom bg = ALG == kBandAlgSeeded   ? band_geom_seeded(m, n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+                        : ALG == kBandAlgExtend ? band_geom_seeded(m, n, (int32_t)P.band, 0)
+                                                : band_geom(m, n, (int32_t)P.band);
     const uint32_t* rec = P.rec + P.recoff[q];
     sa_result* res = P.res + pair;
     uint8_t* ops = P.ops + a1 + a2 + pair;
@@ -453,7 +511,7 @@ __global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
     res->start_i = i;
     res->start_j = j;
     res->nops = nops;
-    res->flags = 0;
+    res->flags = ALG == kBandAlgExtend ? res->flags & SA_FLAG_DROPPED : 0;   // (extension: the fill's flag)
     res->reserved = 0;
 }
 

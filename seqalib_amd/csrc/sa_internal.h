@@ -489,6 +489,12 @@ hipError_t launch_banded_free_tb(bool lut, const BandParams& p, hipStream_t s);
 constexpr int kBandAlgSeeded = 101;
 hipError_t launch_banded_seeded_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_seeded_tb(bool lut, const BandParams& p, hipStream_t s);
+// The NW extension band (sa_banded_extend.hip; sa_align_batch_banded_extend): NW's cell in the band
+// band_geom_seeded(m, n, w, 0), SW's running maximum from (0, 0) on, and the X-drop test.  The call's
+// xdrop (an int32, SA_XDROP_OFF included) travels in BandParams::free_ends; no diagonals follow idx.
+constexpr int kBandAlgExtend = 102;
+hipError_t launch_banded_extend_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
+hipError_t launch_banded_extend_tb(bool lut, const BandParams& p, hipStream_t s);
 
 // The banded affine path (sa_banded_affine.hip; sa_align_batch_banded_affine /
 // sa_score_batch_banded_affine): the first kBandAffineVariants entries of kBandR / kBandL, with three
@@ -519,4 +525,7 @@ hipError_t launch_banded_affine_free_tb(bool lut, const BandAffineParams& p, hip
 // behind idx, as above.
 hipError_t launch_banded_affine_seeded_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_seeded_tb(bool lut, const BandAffineParams& p, hipStream_t s);
+// The GlobalGotoh extension band (sa_banded_affine_extend.hip): as kBandAlgExtend above.
+hipError_t launch_banded_affine_extend_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_extend_tb(bool lut, const BandAffineParams& p, hipStream_t s);
 }  // namespace sa

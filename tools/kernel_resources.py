@@ -30,8 +30,11 @@ ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
 # kMatchFreeBit
 BAND_ALG_FREE, MATCH_FREE_BIT = 100, 8
 BAND_ALG_SEEDED, MATCH_SEED_BIT = 101, 16
+# the extension fills (sa_banded_extend.hip, sa_banded_affine_extend.hip): kBandAlgExtend, and kMatchExtBit alone
+BAND_ALG_EXTEND, MATCH_EXT_BIT = 102, 32
 FREE = {1: "NW free", 3: "GGotoh free"}
 SEEDED = {1: "NW seeded", 3: "GGotoh seeded"}
+EXTEND = {1: "NW extend", 3: "GGotoh extend"}
 MM = ["eq", "lut", "bits", "sub"]
 
 
@@ -53,14 +56,14 @@ def parse(text):
         m = BANDED.search(line)
         if m:   # the banded fills (sa_banded.hip): algorithm, R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
-            cur = {"banded": ((1, 1) if g[0] == BAND_ALG_FREE else (1, 2) if g[0] == BAND_ALG_SEEDED else (g[0], 0)) + g[1:]}
+            cur = {"banded": ((1, 1) if g[0] == BAND_ALG_FREE else (1, 2) if g[0] == BAND_ALG_SEEDED else (1, 3) if g[0] == BAND_ALG_EXTEND else (g[0], 0)) + g[1:]}
             rows.append(cur)
             continue
         m = AFFINE.search(line)
         if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
-            mode = 2 if g[3] & MATCH_SEED_BIT else int(bool(g[3] & MATCH_FREE_BIT))
-            cur = {"banded": (3 - g[0], mode) + g[1:3] + (g[3] & ~(MATCH_FREE_BIT | MATCH_SEED_BIT), g[4])}
+            mode = 3 if g[3] & MATCH_EXT_BIT else 2 if g[3] & MATCH_SEED_BIT else int(bool(g[3] & MATCH_FREE_BIT))
+            cur = {"banded": (3 - g[0], mode) + g[1:3] + (g[3] & ~(MATCH_FREE_BIT | MATCH_SEED_BIT | MATCH_EXT_BIT), g[4])}
             rows.append(cur)
             continue
         m = SO2.search(line)
@@ -97,12 +100,12 @@ def main(argv):
         if not rows and not banded:
             return 0
     if banded:
-        wide = 14 if any(r["banded"][1] == 2 for r in banded) else 8
+        wide = 14 if any(r["banded"][1] >= 2 for r in banded) else 8
         print(f"{'banded':<{wide}}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
         bad_banded = 0
         for r in banded:
             alg, free, R, L, lut, rec = r["banded"]
-            print(f"{SEEDED[alg] if free == 2 else FREE[alg] if free else ALG[alg]:<{wide}}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
+            print(f"{EXTEND[alg] if free == 3 else SEEDED[alg] if free == 2 else FREE[alg] if free else ALG[alg]:<{wide}}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
                   f"{r['Occupancy']:>6}{r['LDS']:>7}")
             bad_banded += r["ScratchSize"] != 0
         print(f"# {len(banded)} banded kernels, {bad_banded} with scratch")
