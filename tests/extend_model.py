@@ -147,10 +147,11 @@ def extend_model(algo, args, s1, s2, w, xdrop, lut=None, trace=None):
 NONE = -(10 ** 15)   # "no such cell" in the numpy fill: below every sum of real scores
 
 
-def extend_fill_np(algo, args, s1, s2, w, xdrop, lut=None):
+def extend_fill_np(algo, args, s1, s2, w, xdrop, lut=None, trace=None):
     """(score, end_i, end_j, dropped, stop_step) of the same sweep, one numpy operation per step: V[c] holds
     the latest cell of diagonal c = j - i - lo', so at step t the diagonals of t's parity hold step t - 2
-    (the diagonal neighbour) and the others step t - 1 (c + 1: the upper neighbour, c - 1: the left one)."""
+    (the diagonal neighbour) and the others step t - 1 (c + 1: the upper neighbour, c - 1: the left one).
+    trace: as extend_model's."""
     assert xdrop >= XDROP_OFF
     g, ma, mi, go, ge, allow = scoring_fields(args)
     affine = algo == GLOBAL_GOTOH
@@ -200,6 +201,8 @@ def extend_fill_np(algo, args, s1, s2, w, xdrop, lut=None):
                     best, end = top, cell
                 recent = top if recent is None else max(recent, top)
         if t % XDROP_PERIOD == XDROP_PERIOD - 1 and t < tend:
+            if recent is not None and trace is not None:
+                trace.append((t, best, recent))
             if recent is not None and xdrop >= 0 and best - recent > xdrop:
                 stop_step = t
                 break
