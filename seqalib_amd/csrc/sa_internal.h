@@ -434,13 +434,13 @@ constexpr int kBandVariants = 8;
 constexpr int kBandR[kBandVariants] = {1, 2, 4, 4, 4, 8, 16, 32};
 constexpr int kBandL[kBandVariants] = {16, 16, 16, 32, 64, 64, 64, 64};
 constexpr int32_t kBandMaxDiagonals = 2 * 32 * 64;
-inline int band_variant(int32_t beff) {   // -1: wider than kBandMaxDiagonals
+__host__ __device__ inline int band_variant(int32_t beff) {   // -1: wider than kBandMaxDiagonals
     for (int v = 0; v < kBandVariants; ++v)
         if (beff <= 2 * kBandR[v] * kBandL[v]) return v;
     return -1;
 }
 // 32-bit record words of a pair: 2 bits per cell slot, step-major ([step group][lane]).
-inline uint64_t band_rec_words(const BandGeom& g, int v) {
+__host__ __device__ inline uint64_t band_rec_words(const BandGeom& g, int v) {
     const uint64_t steps = (uint64_t)(g.tend - g.tb) + 1;
     const int R = kBandR[v], L = kBandL[v];
     return R <= 16 ? (steps + 16 / R - 1) / (16 / R) * L : steps * 2 * L;
@@ -502,12 +502,12 @@ hipError_t launch_banded_extend_tb(bool lut, const BandParams& p, hipStream_t s)
 // kernel uses no scratch (profiles/banded_affine_resources.txt).
 constexpr int kBandAffineVariants = 7;
 constexpr int32_t kBandAffineMaxDiagonals = 2 * kBandR[kBandAffineVariants - 1] * kBandL[kBandAffineVariants - 1];
-inline int band_affine_variant(int32_t beff) {   // -1: wider than kBandAffineMaxDiagonals
+__host__ __device__ inline int band_affine_variant(int32_t beff) {   // -1: wider than kBandAffineMaxDiagonals
     const int v = band_variant(beff);
     return v < kBandAffineVariants ? v : -1;
 }
 // 32-bit record words of a pair: 4 bits per cell slot, step-major ([step group][lane]).
-inline uint64_t band_affine_rec_words(const BandGeom& g, int v) {
+__host__ __device__ inline uint64_t band_affine_rec_words(const BandGeom& g, int v) {
     const uint64_t steps = (uint64_t)(g.tend - g.tb) + 1;
     const int R = kBandR[v], L = kBandL[v];
     return R <= 8 ? (steps + 8 / R - 1) / (8 / R) * L : steps * (R / 8) * L;
