@@ -551,6 +551,67 @@ int sa_score_batch_banded_seeded(sa_ctx* ctx, int algo, const sa_scoring* scorin
 int sa_banded_seeded_plan_query(int algo, uint64_t m, uint64_t n, int32_t diag, uint32_t band, uint32_t free_ends,
                                 int* cells_per_lane, int* pairs_per_wave, uint64_t* ws_bytes_per_pair);
 
+/* Device-resident seeded banded calls: the seeded calls above over two buffers that already lie on the device
+ * -- a mapper's reads and its reference -- so that no window is copied per call.  Every d_ pointer is device
+ * memory.  Pair p is Seq1 = d_seq1[d_start1[p] .. + d_len1[p]) and Seq2 = d_seq2[d_start2[p] .. + d_len2[p]) with
+ * seed diagonal d_diag[p]; slices may overlap and come in any order.  Its ops (traceback order, nops bytes) go to
+ * d_ops + d_ops_off[p], a region that needs room for len1 + len2 + 1 bytes; regions may come in any order and
+ * must not overlap.  max_m / max_n bound the lengths, as in sa_align_batch_device.
+ *
+ * Semantics: for every pair that is run, every field of its sa_result and every op equals what
+ * sa_align_batch_banded_seeded / sa_score_batch_banded_seeded returns for the two slices with the same diag,
+ * band, free_ends, scoring and match table (d_match_lut: a device copy of the 256 x 256 table, or NULL).  The
+ * score call keeps the score contract (start (-1, -1), nops 0).  SA_NW, SA_HIRSCHBERG (= SA_NW) and
+ * SA_GLOBAL_GOTOH.  A pair's fill variant is the narrowest its clipped band fits; the device form never merges
+ * variants (the host call does, unless SEQALIB_BAND_MERGE=0; results do not depend on it).
+ *
+ * Ordering: asynchronous, as sa_align_batch_device.  The call is ordered after the work already on `stream`
+ * (NULL: the context's stream) and after the context's previous call; it plans, fills and walks on that stream
+ * and returns after enqueueing, without a stream synchronisation, a device-to-host copy or a host read of any
+ * length (the context's workspace grows on first use, which drains the context as in every call).
+ * sa_set_pipeline does not change it.  npairs == 0: SA_OK, nothing enqueued.
+ *
+ * Host-side status (made before the context is looked at, so the same with a NULL context; a NULL context with
+ * valid arguments: SA_ERR_ARG): algorithm class, free_ends > 15, band >= 2^31, NULL scoring, gap_extend > 0,
+ * band == 0 without allow_mismatch: as the host seeded calls.  With npairs > 0 a NULL d_start*, d_len*, d_diag,
+ * d_results (align: d_ops, d_ops_off) or a NULL d_seq* with seq*_bytes > 0: SA_ERR_ARG.  From the bound shape
+ * alone -- stricter than the host calls, which judge every pair by its own clipped band -- SA_ERR_UNSUPPORTED for
+ * max_m or max_n >= 2^24; (max_m + max_n + 1) * max(|gap|, |match|, |mismatch|) >= 2^29 (GlobalGotoh:
+ * |gap_open| + |gap_extend| for |gap|, + 10000); min(2 * band + 1, max_m + max_n + 1) above 4096 (NW) or 2048
+ * (GlobalGotoh).  One pair's provision above the workspace limit: SA_ERR_NOMEM.
+ *
+ * Device-side refusals: a refused pair gets an all-zero sa_result with one flag; it writes no op and neither its
+ * slices nor its ops region are touched.  SA_FLAG_BAD_SHAPE, checked first: len1 > max_m, len2 > max_n,
+ * start + len beyond seq*_bytes, (align) ops_off + len1 + len2 + 1 beyond ops_bytes.  SA_FLAG_BAD_BAND: diag
+ * outside [-len1, len2], or the band holds no legal begin or no legal end (the rule of the seeded calls above).
+ *
+ * Workspace: the pairs are run in chunks, contiguous pair ranges one after another on the stream; a chunk's
+ * provision is its pairs x (record_bytes_per_pair + plan_bytes_per_pair) plus 8,704 bytes (a fixed head and
+ * alignment), a score call's the plan bytes only.  record_bytes_per_pair is a bound over every pair inside max_m x max_n at any
+ * diagonal: the records of the variant of min(2 * band + 1, max_m + max_n + 1) diagonals over
+ * min(max_m + max_n, 2 max_m + 2 band, 2 max_n + 2 band) + 2 steps.  sa_banded_seeded_device_plan_query
+ * (host-only) returns both and the cells per lane of that variant.
+ *
+ * sa_last_timings: fill_ms is the planner kernels plus the fills, traceback_ms the walks, launches the chunks.
+ * sa_last_plan_ex: SA_KERNEL_BANDED, the cells per lane of the widest variant a pair inside the bounds can take,
+ * 1 wave, SA_RECORDS_BAND2 / BAND4 / NONE. */
+#define SA_FLAG_BAD_BAND 64   /* device seeded calls: diag outside [-m, n], or the band holds no legal begin / end */
+int sa_align_batch_banded_seeded_device(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                        const uint8_t* d_seq1, uint64_t seq1_bytes, const uint64_t* d_start1, const uint32_t* d_len1,
+                                        const uint8_t* d_seq2, uint64_t seq2_bytes, const uint64_t* d_start2, const uint32_t* d_len2,
+                                        uint32_t npairs, uint32_t max_m, uint32_t max_n, const uint8_t* d_match_lut,
+                                        const int32_t* d_diag, uint32_t band, uint32_t free_ends,
+                                        sa_result* d_results, uint8_t* d_ops, const uint64_t* d_ops_off, uint64_t ops_bytes,
+                                        void* stream);
+int sa_score_batch_banded_seeded_device(sa_ctx* ctx, int algo, const sa_scoring* scoring,
+                                        const uint8_t* d_seq1, uint64_t seq1_bytes, const uint64_t* d_start1, const uint32_t* d_len1,
+                                        const uint8_t* d_seq2, uint64_t seq2_bytes, const uint64_t* d_start2, const uint32_t* d_len2,
+                                        uint32_t npairs, uint32_t max_m, uint32_t max_n, const uint8_t* d_match_lut,
+                                        const int32_t* d_diag, uint32_t band, uint32_t free_ends,
+                                        sa_result* d_results, void* stream);
+int sa_banded_seeded_device_plan_query(int algo, uint32_t max_m, uint32_t max_n, uint32_t band,
+                                       int* widest_cells_per_lane, uint64_t* record_bytes_per_pair, uint64_t* plan_bytes_per_pair);
+
 /* Banded X-drop extension: the alignment mode of a seed-and-extend mapper.  The alignment is anchored at
  * (0, 0), may end at any cell, and a pair's sweep is abandoned once its score has fallen too far below
  * its best.  A caller extends to the right of a seed by passing the two suffixes after the seed, and to

@@ -35,6 +35,7 @@ __all__ = [
     "SA_FLAG_DIVERGED", "SA_FLAG_BAD_SHAPE", "SA_FLAG_SIZE_HACK", "SA_FLAG_TIMEOUT",
     "SA_RECORDS_NONE", "score_plan_query",
     "SA_FLAG_DROPPED", "SA_XDROP_OFF", "SA_XDROP_PERIOD", "banded_extend_plan_query",
+    "SA_FLAG_BAD_BAND", "banded_seeded_device_plan_query",
 ]
 
 SA_SW, SA_NW, SA_LOCAL_GOTOH, SA_GLOBAL_GOTOH, SA_HIRSCHBERG, SA_MYERS_MILLER = 0, 1, 2, 3, 4, 5
@@ -54,6 +55,9 @@ SA_FREE_SEQ1_BEGIN, SA_FREE_SEQ1_END, SA_FREE_SEQ2_BEGIN, SA_FREE_SEQ2_END = 1, 
 # xdrop that never stops one, and the steps between two checkpoints
 SA_FLAG_DROPPED = 32
 SA_XDROP_OFF, SA_XDROP_PERIOD = -1, 16
+# the device-resident seeded calls (sa_align_batch_banded_seeded_device): a pair whose seed diagonal misses its
+# matrix or whose band holds no legal begin / end
+SA_FLAG_BAD_BAND = 64
 SA_HOOK_HAND_TAG, SA_HOOK_POISON_WS, SA_HOOK_F16 = 1, 2, 3   # sa_test_hook (tests only)
 INT32_MIN = -(2 ** 31)
 
@@ -174,6 +178,13 @@ def load_library():
                                                C.c_uint32, C.c_uint32, vp]
     L.sa_banded_seeded_plan_query.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32,
                                               i32p, i32p, u64p]
+    L.sa_align_batch_banded_seeded_device.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, C.c_uint64, vp, vp, vp,
+                                                      C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                                      C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp]
+    L.sa_score_batch_banded_seeded_device.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, C.c_uint64, vp, vp, vp,
+                                                      C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                                      C.c_uint32, C.c_uint32, vp, vp]
+    L.sa_banded_seeded_device_plan_query.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, i32p, u64p, u64p]
     L.sa_align_batch_banded_extend.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
                                                C.c_uint32, C.c_int32, vp, vp, C.c_uint64]
     L.sa_score_batch_banded_extend.argtypes = [vp, C.c_int, C.POINTER(_Scoring), vp, vp, vp, vp, C.c_uint32, vp,
@@ -203,6 +214,8 @@ def load_library():
                "sa_align_batch_banded_ends_free", "sa_score_batch_banded_ends_free",
                "sa_align_batch_banded_seeded", "sa_score_batch_banded_seeded", "sa_banded_seeded_plan_query",
                "sa_align_batch_banded_extend", "sa_score_batch_banded_extend", "sa_banded_extend_plan_query",
+               "sa_align_batch_banded_seeded_device", "sa_score_batch_banded_seeded_device",
+               "sa_banded_seeded_device_plan_query",
                "sa_create", "sa_device_count", "sa_set_pipeline", "sa_wait", "sa_test_hook"):
         getattr(L, fn).restype = C.c_int
     if L.sa_version() != 1:
@@ -853,6 +866,36 @@ class Engine:
                                           max_n, d_lut or None, d_res, d_ops, stream or None)
         self._check(rc, "sa_align_batch_device")
 
+    def align_banded_seeded_device(self, algo: int, scoring: ScoringSystem, d_seq1: int, seq1_bytes: int, d_start1: int,
+                                   d_len1: int, d_seq2: int, seq2_bytes: int, d_start2: int, d_len2: int, npairs: int,
+                                   max_m: int, max_n: int, d_diag: int, band: int, free_ends: int, d_res: int, d_ops: int,
+                                   d_ops_off: int, ops_bytes: int, stream: int = 0, d_lut: int = 0):
+        """Device-resident seeded banded batch (sa_align_batch_banded_seeded_device): pair p is the slices
+        d_seq1[start1[p] .. + len1[p]) and d_seq2[start2[p] .. + len2[p]) of two resident buffers, its ops go to
+        d_ops + ops_off[p].  Pointers are device addresses (uint64 starts and ops offsets, uint32 lengths, int32
+        diagonals); asynchronous on `stream`.  A refused pair has a zero result with SA_FLAG_BAD_SHAPE or
+        SA_FLAG_BAD_BAND."""
+        sc = scoring._c()
+        rc = self.L.sa_align_batch_banded_seeded_device(
+            self.h, algo, C.byref(sc), d_seq1 or None, seq1_bytes, d_start1 or None, d_len1 or None, d_seq2 or None,
+            seq2_bytes, d_start2 or None, d_len2 or None, npairs, max_m, max_n, d_lut or None, d_diag or None,
+            _band_arg(band), _free_ends_arg(free_ends), d_res or None, d_ops or None, d_ops_off or None, ops_bytes,
+            stream or None)
+        self._check(rc, "sa_align_batch_banded_seeded_device")
+
+    def score_banded_seeded_device(self, algo: int, scoring: ScoringSystem, d_seq1: int, seq1_bytes: int, d_start1: int,
+                                   d_len1: int, d_seq2: int, seq2_bytes: int, d_start2: int, d_len2: int, npairs: int,
+                                   max_m: int, max_n: int, d_diag: int, band: int, free_ends: int, d_res: int,
+                                   stream: int = 0, d_lut: int = 0):
+        """Scores and end cells of align_banded_seeded_device's pairs (sa_score_batch_banded_seeded_device):
+        start = (-1, -1), nops = 0; no records, no walk, no ops."""
+        sc = scoring._c()
+        rc = self.L.sa_score_batch_banded_seeded_device(
+            self.h, algo, C.byref(sc), d_seq1 or None, seq1_bytes, d_start1 or None, d_len1 or None, d_seq2 or None,
+            seq2_bytes, d_start2 or None, d_len2 or None, npairs, max_m, max_n, d_lut or None, d_diag or None,
+            _band_arg(band), _free_ends_arg(free_ends), d_res or None, stream or None)
+        self._check(rc, "sa_score_batch_banded_seeded_device")
+
     # ---- score-only calls: scores and end cells, no traceback (include/seqalib_hip.h sa_score_batch)
     def score_packed(self, algo: int, scoring: ScoringSystem, s1: np.ndarray, off1: np.ndarray,
                      s2: np.ndarray, off2: np.ndarray, lut: Optional[np.ndarray] = None) -> np.ndarray:
@@ -1016,6 +1059,18 @@ def banded_seeded_plan_query(algo: int, m: int, n: int, diag: int, band: int, fr
     if rc:
         raise SeqalibError(f"sa_banded_seeded_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
     return R.value, ppw.value, ws.value
+
+
+def banded_seeded_device_plan_query(algo: int, max_m: int, max_n: int, band: int):
+    """(cells per lane of the widest variant a pair inside max_m x max_n can take, record bytes provisioned per
+    pair, plan bytes per pair) of the device-resident seeded calls (sa_banded_seeded_device_plan_query).  Raises
+    where the calls refuse the bound shape."""
+    L = load_library()
+    R, rec, plan = C.c_int(), C.c_uint64(), C.c_uint64()
+    rc = L.sa_banded_seeded_device_plan_query(algo, max_m, max_n, _band_arg(band), C.byref(R), C.byref(rec), C.byref(plan))
+    if rc:
+        raise SeqalibError(f"sa_banded_seeded_device_plan_query: {L.sa_status_string(rc).decode()} ({L.sa_last_error(None).decode()})")
+    return R.value, rec.value, plan.value
 
 
 def banded_extend_plan_query(algo: int, m: int, n: int, band: int):

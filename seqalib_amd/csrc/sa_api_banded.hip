@@ -11,6 +11,7 @@
 
 #include "sa_api_ctx.h"
 #include "sa_band_group.h"
+#include "sa_band_plan.h"
 
 using namespace sa;
 
@@ -51,25 +52,13 @@ struct BandCall {
     int32_t xdrop = SA_XDROP_OFF;
 };
 
-constexpr CallRules kLinearRules = {
-    .algos = 1u << SA_SW | 1u << SA_NW | 1u << SA_HIRSCHBERG,
-    .unsupported = "banded calls support the linear-gap algorithms only (SA_SW, SA_NW, SA_HIRSCHBERG)",
-    .band = kBandOverflow, .band0 = true};
-constexpr CallRules kAffineRules = {
-    .algos = 1u << SA_LOCAL_GOTOH | 1u << SA_GLOBAL_GOTOH,
-    .unsupported = "banded affine calls support SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH only",
-    .gap_extend = true, .band = kBandOverflow, .band0 = true};
-constexpr uint32_t kAlgoGlobal = 1u << SA_NW | 1u << SA_HIRSCHBERG | 1u << SA_GLOBAL_GOTOH;
+// (kLinearRules, kAffineRules, kAlgoGlobal and kSeededRules: sa_api_ctx.h, shared with sa_api_banded_device.hip)
 // the ends-free and seeded calls' own checks; the linear or affine rules of their algorithm follow
 // (banded_batch), for the seeded calls behind the diag checks
 constexpr CallRules kEndsFreeRules = {
     .algos = kAlgoGlobal,
     .unsupported = "ends-free banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only",
     .free_ends = true};
-constexpr CallRules kSeededRules = {
-    .algos = kAlgoGlobal,
-    .unsupported = "seeded banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only",
-    .free_ends = true, .band_early = "band: 2 * band + 1 diagonals overflow 32 bits"};
 constexpr CallRules kExtendRules = {
     .algos = kAlgoGlobal,
     .unsupported = "banded extension calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only",
@@ -127,12 +116,9 @@ struct BandSeed {
 
 // The seeded legality rule: the band must hold a legal begin and a legal end (include/seqalib_hip.h).
 int banded_seed_legal(sa_ctx* c, const BandSeed& sd, const BandGeom& g, int64_t m, int64_t n) {
-    const bool begin = (g.lo <= 0 && 0 <= g.hi) || ((sd.free_ends & kFreeSeq2Begin) && g.hi >= 0) ||
-                       ((sd.free_ends & kFreeSeq1Begin) && g.lo <= 0);
-    const int64_t d = n - m;
-    const bool end = (g.lo <= d && d <= g.hi) || ((sd.free_ends & kFreeSeq2End) && g.lo <= d) ||
-                     ((sd.free_ends & kFreeSeq1End) && g.hi >= d);
-    if (begin && end) return SA_OK;
+    const int legal = band_seed_legality(g, m, n, sd.free_ends);   // (sa_band_plan.h: the device planner's rule too)
+    const bool begin = legal & 1, end = legal & 2;
+    if (legal == kBandSeedLegal) return SA_OK;
     return fail(c, SA_ERR_UNSUPPORTED,
                 "pair " + std::to_string(sd.pair) + ": the band [" + std::to_string(g.lo) + ", " + std::to_string(g.hi) +
                     "] holds no legal " + (begin ? "end" : end ? "begin" : "begin and no legal end") +

@@ -137,6 +137,21 @@ constexpr const char* kMatrixAlgos = "matrix calls support SA_SW, SA_NW, SA_LOCA
 // sa_align_batch_matrix / sa_score_batch_matrix / sa_matrix_plan_query, and the matrix band calls
 constexpr CallRules kMatrixRules = {.algos = kAlgoMatrix, .unsupported = kMatrixAlgos};
 constexpr CallRules kBandedMatrixRules = {.algos = kAlgoMatrix, .unsupported = kMatrixAlgos, .gap_extend = true, .band = kBandOverflow};
+// the banded calls (sa_api_banded.hip) and the device-resident seeded ones (sa_api_banded_device.hip): the
+// linear and affine bands' rules, and the seeded calls' own, which run ahead of their algorithm's
+constexpr CallRules kLinearRules = {
+    .algos = 1u << SA_SW | 1u << SA_NW | 1u << SA_HIRSCHBERG,
+    .unsupported = "banded calls support the linear-gap algorithms only (SA_SW, SA_NW, SA_HIRSCHBERG)",
+    .band = kBandOverflow, .band0 = true};
+constexpr CallRules kAffineRules = {
+    .algos = 1u << SA_LOCAL_GOTOH | 1u << SA_GLOBAL_GOTOH,
+    .unsupported = "banded affine calls support SA_LOCAL_GOTOH and SA_GLOBAL_GOTOH only",
+    .gap_extend = true, .band = kBandOverflow, .band0 = true};
+constexpr uint32_t kAlgoGlobal = 1u << SA_NW | 1u << SA_HIRSCHBERG | 1u << SA_GLOBAL_GOTOH;
+constexpr CallRules kSeededRules = {
+    .algos = kAlgoGlobal,
+    .unsupported = "seeded banded calls support the global algorithms SA_NW, SA_HIRSCHBERG and SA_GLOBAL_GOTOH only",
+    .free_ends = true, .band_early = "band: 2 * band + 1 diagonals overflow 32 bits"};
 
 inline int check_call(sa_ctx* c, const CallRules& r, int algo, const sa_scoring* sc, uint32_t band, uint32_t free_ends) {
     if (!sc) return fail(c, SA_ERR_ARG, "scoring is NULL");

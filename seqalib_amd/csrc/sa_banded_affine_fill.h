@@ -37,7 +37,12 @@
 // sa_banded_affine_extend.hip): GlobalGotoh's cell and borders in the band band_geom_seeded(m, n, w, 0),
 // the local mode's running `best` over M of the interior cells, from the key of (0, 0) on, and the X-drop
 // test with its wave-uniform early exit, all as sa_banded_fill.h describes them.
+//
+// Device-planned seeded mode (kMatchPlanBit beside the seeded mode's two; the sa_*_batch_banded_seeded_device
+// calls, instantiated by sa_banded_affine_seeded_dev.hip): the launch is described in device memory, as in
+// sa_banded_fill.h -- off1 the plan records, off2 this variant's {first entry, length}, idx the lists.
 #pragma once
+#include "sa_band_plan.h"
 #include "sa_internal.h"
 
 namespace sa {
@@ -47,6 +52,7 @@ constexpr int32_t kBorderXY = -10000;   // X and Y of every border cell (the ref
 constexpr int kMatchFreeBit = 8;        // in the fill kernel's match-mode template value: the ends-free mode
 constexpr int kMatchSeedBit = 16;       // with kMatchFreeBit: the seeded band (band_geom_seeded, diagonals behind idx)
 constexpr int kMatchExtBit = 32;        // alone: the extension mode (xdrop in BandParams::free_ends)
+constexpr int kMatchPlanBit = 64;       // with kMatchFreeBit | kMatchSeedBit: the pairs come from plan records
 
 __device__ __forceinline__ int32_t aff_from_lower_lane(int32_t v) {   // lane l takes lane l - 1's, lane 0 kBandNeg
     return __builtin_amdgcn_update_dpp(kBandNeg, v, 0x138, 0xf, 0xf, false);
@@ -186,11 +192,20 @@ struct BandAffineFill {
 
 template <bool LOCAL, int R, int L, int MMF, bool REC>   // MMF: the match mode [| kMatchFreeBit [| kMatchSeedBit] | kMatchExtBit]
 __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams P) {
-    constexpr int MM = MMF & ~(kMatchFreeBit | kMatchSeedBit | kMatchExtBit);
+    constexpr int MM = MMF & ~(kMatchFreeBit | kMatchSeedBit | kMatchExtBit | kMatchPlanBit);
     constexpr bool FREE = (MMF & kMatchFreeBit) != 0, SEEDED = (MMF & kMatchSeedBit) != 0, EXT = (MMF & kMatchExtBit) != 0;
+    constexpr bool PLANNED = (MMF & kMatchPlanBit) != 0;
     static_assert(FREE || !SEEDED, "the seeded band is an ends-free one");
+    static_assert(SEEDED || !PLANNED, "the planned mode is the seeded band's");
     using F = BandAffineFill<LOCAL, R, L, MM, REC, FREE, EXT>;
     constexpr int PPW = 64 / L, S = F::S, WPS = F::WPS;
+    uint32_t lfirst = 0, lcount = 0;
+    if (PLANNED) {   // the list's place and length, from device memory
+        const uint32_t* const li = reinterpret_cast<const uint32_t*>(P.off2);
+        lfirst = li[0];
+        lcount = li[1];
+        if (blockIdx.x * PPW >= lcount) return;   // (the whole block: the grid covers a full chunk)
+    }
     __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
     if (MM == kMatchLut) {
         for (int k = threadIdx.x; k < 2048; k += 64) lut_s[k] = P.lutbits[k];
@@ -207,14 +222,26 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
     F f;
     f.l = lane % L;
     const uint32_t q = blockIdx.x * PPW + g;
-    const bool live = q < P.count;
+    const bool live = q < (PLANNED ? lcount : P.count);
     uint32_t pair = 0;
     const uint8_t* s1 = P.seq1;
     const uint8_t* s2 = P.seq2;
     f.m = 0;
     f.n = 0;
     BandGeom bg{0, 0, 0, 0x7ffffffe, -1};
-    if (live) {
+    uint64_t plan_recoff = 0;
+    if (PLANNED) {
+        if (live) {
+            const BandPlanRec& pr = reinterpret_cast<const BandPlanRec*>(P.off1)[P.idx[lfirst + q]];
+            pair = pr.pair;
+            f.m = pr.m;
+            f.n = pr.n;
+            s1 = pr.s1;
+            s2 = pr.s2;
+            plan_recoff = pr.recoff;
+            bg = band_geom_seeded(f.m, f.n, (int32_t)P.band, pr.diag);
+        }
+    } else if (live) {
         pair = P.idx[q];
         const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
         f.m = (int32_t)(P.off1[pair + 1] - a1);
@@ -283,7 +310,7 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
 #pragma unroll
     for (int r = 0; r <= R; ++r) f.Bw[r] = sym2(h0 + bb + r);
 
-    uint32_t* rec = REC && live ? P.rec + P.recoff[q] : nullptr;
+    uint32_t* rec = REC && live ? P.rec + (PLANNED ? plan_recoff : P.recoff[q]) : nullptr;
     uint32_t acc = 0;
     auto store = [&](int32_t t) {
         if (!REC) return;

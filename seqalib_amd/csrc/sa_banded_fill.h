@@ -66,7 +66,17 @@
 // sweep's last iteration h1 is then taken again over the pairs still running, so a wave whose pairs
 // have all stopped leaves the loop at once; the exit is wave-uniform and nothing waits.  xdrop (the same
 // for every pair) travels in BandParams::free_ends, which no other part of this mode reads.
+//
+// Device-planned seeded mode (ALG = kBandAlgSeededDev, the sa_*_batch_banded_seeded_device calls; instantiated
+// by sa_banded_seeded_dev.hip): the seeded mode with the launch described in device memory.  BandParams keeps
+// its layout and is read differently: off1 holds the chunk's plan records (BandPlanRec, sa_band_plan.h), off2
+// the {first entry, length} of this variant's list, idx the chunk's lists (entries are plan record numbers),
+// count the pairs of the chunk (what the grid covers).  A block past the list's length returns before it
+// touches anything; a pair's slices, lengths, diagonal, record offset, ops offset and result index come from
+// its plan record.  The mode is a value of ALG, not a template parameter of its own, so that the names -- and
+// with them the code objects -- of the other modes' kernels stay as they are.
 #pragma once
+#include "sa_band_plan.h"
 #include "sa_internal.h"
 
 namespace sa {
@@ -81,7 +91,7 @@ __device__ __forceinline__ int32_t from_upper_lane(int32_t v) {   // lane l take
 
 template <int ALG, int R, int L, int MM, bool REC>
 struct BandFill {
-    static constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded;
+    static constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded || ALG == kBandAlgSeededDev;
     static constexpr bool EXT = ALG == kBandAlgExtend;   // NW's cell and borders throughout
     static constexpr int S = R <= 16 ? 16 / R : 1;   // steps per record word
     int32_t E[R], O[R];
@@ -195,6 +205,14 @@ template <int ALG, int R, int L, int MM, bool REC>
 __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
     using F = BandFill<ALG, R, L, MM, REC>;
     constexpr int PPW = 64 / L, S = F::S;
+    constexpr bool PLANNED = ALG == kBandAlgSeededDev;
+    uint32_t lfirst = 0, lcount = 0;
+    if (PLANNED) {   // the list's place and length, from device memory
+        const uint32_t* const li = reinterpret_cast<const uint32_t*>(P.off2);
+        lfirst = li[0];
+        lcount = li[1];
+        if (blockIdx.x * PPW >= lcount) return;   // (the whole block: the grid covers a full chunk)
+    }
     __shared__ uint32_t lut_s[MM != kMatchEq ? 2048 : 1];
     if (MM == kMatchLut) {
         for (int k = threadIdx.x; k < 2048; k += 64) lut_s[k] = P.lutbits[k];
@@ -211,14 +229,26 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
     F f;
     f.l = lane % L;
     const uint32_t q = blockIdx.x * PPW + g;
-    const bool live = q < P.count;
+    const bool live = q < (PLANNED ? lcount : P.count);
     uint32_t pair = 0;
     const uint8_t* s1 = P.seq1;
     const uint8_t* s2 = P.seq2;
     f.m = 0;
     f.n = 0;
     BandGeom bg{0, 0, 0, 0x7ffffffe, -1};
-    if (live) {
+    uint64_t plan_recoff = 0;
+    if (PLANNED) {
+        if (live) {
+            const BandPlanRec& pr = reinterpret_cast<const BandPlanRec*>(P.off1)[P.idx[lfirst + q]];
+            pair = pr.pair;
+            f.m = pr.m;
+            f.n = pr.n;
+            s1 = pr.s1;
+            s2 = pr.s2;
+            plan_recoff = pr.recoff;
+            bg = band_geom_seeded(f.m, f.n, (int32_t)P.band, pr.diag);
+        }
+    } else if (live) {
         pair = P.idx[q];
         const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
         f.m = (int32_t)(P.off1[pair + 1] - a1);
@@ -285,7 +315,7 @@ __global__ __launch_bounds__(64) void banded_fill_kernel(BandParams P) {
 #pragma unroll
     for (int r = 0; r <= R; ++r) f.Bw[r] = sym2(h0 + bb + r);
 
-    uint32_t* rec = REC && live ? P.rec + P.recoff[q] : nullptr;
+    uint32_t* rec = REC && live ? P.rec + (PLANNED ? plan_recoff : P.recoff[q]) : nullptr;
     uint32_t acc = 0;
     auto store = [&](int32_t t) {
         if (!REC) return;
@@ -459,21 +489,48 @@ hipError_t launch_band_fill_alg(int variant, bool rec, const BandParams& p, hipS
 // (kBandAlgExtend): it starts at the fill's end cell too, walks to (0, 0) and keeps the fill's flag.
 template <int ALG, bool LUT>
 __global__ __launch_bounds__(64) void banded_tb_kernel(BandParams P) {
-    constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded;
+    constexpr bool FREE = ALG == kBandAlgFree || ALG == kBandAlgSeeded || ALG == kBandAlgSeededDev;
+    constexpr bool PLANNED = ALG == kBandAlgSeededDev;   // one launch over the chunk's plan records, R and L per pair
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= P.count) return;
-    const uint32_t pair = P.idx[q];
-    const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
-    const int32_t m = (int32_t)(P.off1[pair + 1] - a1), n = (int32_t)(P.off2[pair + 1] - a2);
-    const uint8_t* s1 = P.seq1 + a1;
-    const uint8_t* s2 = P.seq2 + a2;
-    const BandGeom bg = ALG == kBandAlgSeeded   ? band_geom_seeded(m, n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
-                        : ALG == kBandAlgExtend ? band_geom_seeded(m, n, (int32_t)P.band, 0)
-                                                : band_geom(m, n, (int32_t)P.band);
-    const uint32_t* rec = P.rec + P.recoff[q];
+    uint32_t pair;
+    int32_t m, n;
+    const uint8_t* s1;
+    const uint8_t* s2;
+    BandGeom bg;
+    const uint32_t* rec;
+    uint8_t* ops;
+    int R, L;
+    if (PLANNED) {
+        const BandPlanRec& pr = reinterpret_cast<const BandPlanRec*>(P.off1)[q];
+        if (pr.v < 0) return;   // refused by the planner: its result is written, it has no ops
+        pair = pr.pair;
+        m = pr.m;
+        n = pr.n;
+        s1 = pr.s1;
+        s2 = pr.s2;
+        bg = band_geom_seeded(m, n, (int32_t)P.band, pr.diag);
+        rec = P.rec + pr.recoff;
+        ops = P.ops + pr.opsoff;
+        R = kBandR[pr.v];
+        L = kBandL[pr.v];
+    } else {
+        pair = P.idx[q];
+        const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
+        m = (int32_t)(P.off1[pair + 1] - a1);
+        n = (int32_t)(P.off2[pair + 1] - a2);
+        s1 = P.seq1 + a1;
+        s2 = P.seq2 + a2;
+        bg = ALG == kBandAlgSeeded   ? band_geom_seeded(m, n, (int32_t)P.band, (int32_t)P.idx[P.count + q])
+             : ALG == kBandAlgExtend ? band_geom_seeded(m, n, (int32_t)P.band, 0)
+                                     : band_geom(m, n, (int32_t)P.band);
+        rec = P.rec + P.recoff[q];
+        ops = P.ops + a1 + a2 + pair;
+        R = P.R;
+        L = P.L;
+    }
     sa_result* res = P.res + pair;
-    uint8_t* ops = P.ops + a1 + a2 + pair;
-    const int R = P.R, L = P.L, S = R <= 16 ? 16 / R : 1;
+    const int S = R <= 16 ? 16 / R : 1;
     int32_t i = res->end_i, j = res->end_j;
     if (ALG == SA_SW && (m == 0 || n == 0)) i = j = 0;
     if (i < 0 || i > m || j < 0 || j > n) i = j = 0;   // (never: the fill's end cell is a cell)

@@ -489,6 +489,15 @@ hipError_t launch_banded_free_tb(bool lut, const BandParams& p, hipStream_t s);
 constexpr int kBandAlgSeeded = 101;
 hipError_t launch_banded_seeded_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_seeded_tb(bool lut, const BandParams& p, hipStream_t s);
+// The device-planned seeded band (sa_banded_seeded_dev.hip, sa_banded_affine_seeded_dev.hip;
+// sa_align_batch_banded_seeded_device): the seeded fills and walks over pairs a planner kernel described in
+// device memory (sa_band_plan.h BandPlanRec, sa_band_planner.hip).  BandParams is read differently there:
+// off1 = the chunk's plan records, off2 = the {first entry, length} words of the variant's list (fills),
+// idx = the chunk's lists, count = the pairs of the chunk -- the fill grid covers that many in every variant,
+// the walk's one launch that many plan records; recoff, seq1, seq2, R and L are not read.
+constexpr int kBandAlgSeededDev = 103;
+hipError_t launch_banded_seeded_dev_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
+hipError_t launch_banded_seeded_dev_tb(bool lut, const BandParams& p, hipStream_t s);
 // The NW extension band (sa_banded_extend.hip; sa_align_batch_banded_extend): NW's cell in the band
 // band_geom_seeded(m, n, w, 0), SW's running maximum from (0, 0) on, and the X-drop test.  The call's
 // xdrop (an int32, SA_XDROP_OFF included) travels in BandParams::free_ends; no diagonals follow idx.
@@ -525,6 +534,9 @@ hipError_t launch_banded_affine_free_tb(bool lut, const BandAffineParams& p, hip
 // behind idx, as above.
 hipError_t launch_banded_affine_seeded_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_seeded_tb(bool lut, const BandAffineParams& p, hipStream_t s);
+// The device-planned seeded GlobalGotoh band (sa_banded_affine_seeded_dev.hip): as kBandAlgSeededDev above.
+hipError_t launch_banded_affine_seeded_dev_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
+hipError_t launch_banded_affine_seeded_dev_tb(bool lut, const BandAffineParams& p, hipStream_t s);
 // The GlobalGotoh extension band (sa_banded_affine_extend.hip): as kBandAlgExtend above.
 hipError_t launch_banded_affine_extend_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_extend_tb(bool lut, const BandAffineParams& p, hipStream_t s);
