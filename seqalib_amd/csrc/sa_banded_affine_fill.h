@@ -405,9 +405,11 @@ __global__ __launch_bounds__(64) void banded_affine_fill_kernel(BandAffineParams
         }
         sc = (int32_t)(b >> 32);
         const uint32_t pos = (uint32_t)b;
-        // (an idle lane group has beff = 0: the division does not trap, and only live pairs are written below)
-        sc_i = (int32_t)(pos / (uint32_t)f.beff);
-        sc_j = sc_i + f.lo + (int32_t)(pos % (uint32_t)f.beff);
+        // (an idle lane group has beff = 0 and divides by 1: a division by zero is undefined, and the CPU run of
+        // this source, tests/test_banded_emu.py, traps on it; only live pairs are written below)
+        const uint32_t bdiv = (uint32_t)max(f.beff, 1);
+        sc_i = (int32_t)(pos / bdiv);
+        sc_j = sc_i + f.lo + (int32_t)(pos % bdiv);
     } else if (FREE) {   // (m, n) is a candidate of every pair, so b is a cell's key
         f.end_cell();
         long long b = f.best;

@@ -216,7 +216,7 @@ def cells_per_lane(diagonals):
     return next(R for R, L in VARIANTS if diagonals <= 2 * R * L)
 
 
-def variant_batch(sizes, clipped, seed):
+def variant_batch(sizes, clipped, seed, upload=True):
     """Pairs m = n = s seeded at diagonal 0 (with w >= s the clipped band holds 2s + 1 diagonals), five pairs of
     3 x 3 -- the narrowest variant, one wave with idle groups -- and, when asked for, the clipped pair 40 x 1073."""
     rng = np.random.default_rng(seed)
@@ -229,7 +229,8 @@ def variant_batch(sizes, clipped, seed):
         pairs.append((a, edited(rng, a) + seq(rng, ACGT, 1073)))
         pairs[-1] = (a, pairs[-1][1][:1073])
     order = [int(x) for x in np.random.default_rng(seed + 1).permutation(len(pairs))]   # the variants interleaved
-    return Batch.packed([pairs[p] for p in order], [0] * len(pairs)).upload()
+    b = Batch.packed([pairs[p] for p in order], [0] * len(pairs))
+    return b.upload() if upload else b   # (tests/test_banded_emu.py runs the same batch without a device)
 
 
 def check_variants(engine, monkeypatch, algo, sizes, clipped, w, top):
@@ -267,7 +268,7 @@ def test_gg64_lanes_per_pair(engine, monkeypatch):
 
 
 # ------------------------------------------------------------------------- 4. refusals among valid pairs
-def refusal_batch():
+def refusal_batch(upload=True):
     """Valid pairs (legal under free_ends = 0 at w = 3) with one pair for each refusal between them.
     Returns the batch, {pair: flag} for the align call, and the pairs only the align call refuses."""
     pairs, diags = legal_batch(11, 3, 0, 12)
@@ -307,7 +308,7 @@ def refusal_batch():
         elif not reason.startswith("len"):
             flags[p] = sa.SA_FLAG_BAD_BAND
     align_only = [p for p, r in why.items() if r.startswith("ops")]
-    return b.upload(), flags, align_only
+    return (b.upload() if upload else b), flags, align_only
 
 
 @pytest.mark.parametrize("algo", ALGOS)
