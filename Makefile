@@ -25,7 +25,7 @@ HIP_SRCS  = $(CSRC)/sa_fill_sw.hip $(CSRC)/sa_fill_so2.hip $(CSRC)/sa_fill_nw.hi
             $(CSRC)/sa_band_planner.hip $(CSRC)/sa_banded_seeded_dev.hip $(CSRC)/sa_banded_affine_seeded_dev.hip \
             $(CSRC)/sa_api_banded_device.hip
 CPP_SRCS  = $(CSRC)/sa_synth.cpp $(CSRC)/sa_multi.cpp $(CSRC)/sa_codec.cpp
-HDRS      = $(CSRC)/sa_internal.h $(CSRC)/sa_layout.h $(CSRC)/sa_fill_impl.h $(CSRC)/sa_dc.h $(CSRC)/sa_banded_fill.h $(CSRC)/sa_banded_affine_fill.h $(CSRC)/sa_api_ctx.h $(CSRC)/sa_band_group.h $(CSRC)/sa_band_plan.h include/seqalib_hip.h
+HDRS      = $(CSRC)/sa_internal.h $(CSRC)/sa_layout.h $(CSRC)/sa_fill_impl.h $(CSRC)/sa_dc.h $(CSRC)/sa_band_sweep.h $(CSRC)/sa_banded_fill.h $(CSRC)/sa_banded_affine_fill.h $(CSRC)/sa_api_ctx.h $(CSRC)/sa_band_group.h $(CSRC)/sa_band_plan.h include/seqalib_hip.h
 OBJS      = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(CPP_SRCS))
 
 lib: $(LIB)

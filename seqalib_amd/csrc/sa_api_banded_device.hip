@@ -153,7 +153,7 @@ int seeded_device_batch(sa_ctx* c, const SeededDeviceCall& k) {
         pp.head = head;
         pp.plans = plans;
         pp.lists = lists;
-        BandAffineParams bp;   // (the linear launchers take its BandParams base); read as sa_internal.h kBandAlgSeededDev says
+        BandAffineParams bp;   // (the linear launchers take its BandParams base); read as sa_internal.h kBandSeededDev says
         bp.seq1 = k.seq1;
         bp.off1 = reinterpret_cast<const uint64_t*>(plans);
         bp.seq2 = k.seq2;

@@ -120,7 +120,7 @@ inline bool band_group(const BandGroupIn& in, BandGroups* out) {
 }
 
 // The seeded calls' uploaded index array: each launch's block is [its idx entries][their diagonals]
-// (sa_internal.h kBandAlgSeeded), so launch ln's block starts at 2 * ln.first.
+// (sa_internal.h kBandSeeded), so launch ln's block starts at 2 * ln.first.
 inline std::vector<uint32_t> band_idx_with_diagonals(const BandGroups& g, const int32_t* diag) {
     std::vector<uint32_t> both;
     both.reserve(2 * g.idx.size());

@@ -1,89 +1,18 @@
-// Ends-free instantiations of the banded GlobalGotoh fill (sa_align_batch_banded_ends_free,
+// Ends-free (kBandFree) instantiations of the banded GlobalGotoh fill and walk (sa_align_batch_banded_ends_free,
 // sa_score_batch_banded_ends_free with SA_GLOBAL_GOTOH): kMatchEq and kMatchLut, recording and
-// record-free, every affine variant, and their walk.  A translation unit of their own, so
-// sa_banded_affine.hip's code object is unchanged.  DESIGN.md §2.15.
+// record-free, every affine variant.  A translation unit of their own, so sa_banded_affine.hip's code
+// object is unchanged.  DESIGN.md §2.15.
 #include "sa_banded_affine_fill.h"
 
 namespace sa {
-namespace {
-
-// The ends-free walk: banded_affine_tb_kernel's GlobalGotoh walk (sa_banded_affine.hip: the same
-// records, `type` state machine and op codes) from the fill's end cell, in type 0, to a border, where
-// it stops if that begin is free.  A kernel of its own: banded_affine_tb_kernel's template parameters
-// are two bools, so a mode could only be added by renaming the existing instances.
-template <bool LUT>
-__global__ __launch_bounds__(64) void banded_affine_free_tb_kernel(BandAffineParams P) {
-    const uint32_t q = blockIdx.x * 64 + threadIdx.x;
-    if (q >= P.count) return;
-    const uint32_t pair = P.idx[q];
-    const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
-    const int32_t m = (int32_t)(P.off1[pair + 1] - a1), n = (int32_t)(P.off2[pair + 1] - a2);
-    const uint8_t* s1 = P.seq1 + a1;
-    const uint8_t* s2 = P.seq2 + a2;
-    const BandGeom bg = band_geom(m, n, (int32_t)P.band);
-    const uint32_t* rec = P.rec + P.recoff[q];
-    sa_result* res = P.res + pair;
-    uint8_t* ops = P.ops + a1 + a2 + pair;
-    const int R = P.R, L = P.L, S = R <= 8 ? 8 / R : 1, WPS = R <= 8 ? 1 : R / 8;
-    const bool stop_i0 = (P.free_ends & kFreeSeq2Begin) != 0, stop_j0 = (P.free_ends & kFreeSeq1Begin) != 0;
-    int32_t i = res->end_i, j = res->end_j;
-    if (i < 0 || i > m || j < 0 || j > n) i = j = 0;   // (never: the fill's end cell is a cell)
-    uint32_t nops = 0;
-    const uint32_t cap = (uint32_t)(m + n);            // (never reached: every op consumes a symbol)
-    int type = 0;
-    while ((i > 0 || j > 0) && nops < cap) {
-        if ((i == 0 && stop_i0) || (j == 0 && stop_j0)) break;
-        if (i == 0) { ops[nops++] = 'L'; --j; continue; }
-        if (j == 0) { ops[nops++] = 'U'; --i; continue; }
-        const int32_t tp = i + j - bg.lo - bg.tb, c = j - i - bg.lo;
-        if (c < 0 || c >= bg.beff) break;   // (never: the walk stays inside the band)
-        const int32_t l = c / (2 * R), rr = (c % (2 * R)) >> 1;
-        uint32_t w;
-        if (R <= 8) w = rec[(uint64_t)(tp / S) * L + l] >> (((tp % S) * R + rr) * 4);
-        else w = rec[((uint64_t)tp * WPS + (rr >> 3)) * L + l] >> ((rr & 7) * 4);
-        if (type == 0) {
-            const uint32_t code = w & 3u;
-            if (code == 0) break;   // (never: a global cell's M has a source)
-            if (code == 1) {
-                const uint32_t a = s1[i - 1], b = s2[j - 1];
-                const bool v = LUT ? ((P.lutbits[(a << 3) | (b >> 5)] >> (b & 31)) & 1u) != 0 : a == b;
-                ops[nops++] = (v || P.allow) ? (v ? 'M' : 'S') : 'X';
-                --i;
-                --j;
-                continue;
-            }
-            type = (int)code - 1;
-        }
-        if (type == 1) {
-            ops[nops++] = 'U';
-            --i;
-            if (!(w & 4u)) type = 0;
-        } else {
-            ops[nops++] = 'L';
-            --j;
-            if (!(w & 8u)) type = 0;
-        }
-    }
-    res->start_i = i;
-    res->start_j = j;
-    res->nops = nops;
-    res->flags = 0;
-    res->reserved = 0;
-}
-
-}  // namespace
-
 hipError_t launch_banded_affine_free_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
-    return lut ? launch_band_affine_fill_alg<false, kMatchLut | kMatchFreeBit>(variant, rec, p, s)
-               : launch_band_affine_fill_alg<false, kMatchEq | kMatchFreeBit>(variant, rec, p, s);
+    return lut ? launch_band_sweep<BandAffineFill, SA_GLOBAL_GOTOH, kBandFree, kMatchLut>(variant, rec, p, s)
+               : launch_band_sweep<BandAffineFill, SA_GLOBAL_GOTOH, kBandFree, kMatchEq>(variant, rec, p, s);
 }
 
 hipError_t launch_banded_affine_free_tb(bool lut, const BandAffineParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
-    const dim3 grid((p.count + 63) / 64), block(64);
-    if (lut) hipLaunchKernelGGL((banded_affine_free_tb_kernel<true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((banded_affine_free_tb_kernel<false>), grid, block, 0, s, p);
-    return hipGetLastError();
+    return launch_band_affine_tb<kBandFree>(SA_GLOBAL_GOTOH, lut, p, s);
 }
 }  // namespace sa

@@ -1,91 +1,19 @@
-// Seeded instantiations of the banded GlobalGotoh fill (sa_align_batch_banded_seeded,
+// Seeded (kBandSeeded) instantiations of the banded GlobalGotoh fill and walk (sa_align_batch_banded_seeded,
 // sa_score_batch_banded_seeded with SA_GLOBAL_GOTOH): the ends-free mode with every pair's band placed
-// round its seed diagonal (kMatchFreeBit | kMatchSeedBit).  kMatchEq and kMatchLut, recording and
-// record-free, every affine variant, and their walk.  A translation unit of their own, so the code
-// objects of sa_banded_affine.hip and sa_banded_affine_free.hip are unchanged.  DESIGN.md §2.16.
+// round its seed diagonal, read from behind the launch's idx entries.  kMatchEq and kMatchLut, recording and
+// record-free, every affine variant.  A translation unit of their own, so the code objects of
+// sa_banded_affine.hip and sa_banded_affine_free.hip are unchanged.  DESIGN.md §2.16.
 #include "sa_banded_affine_fill.h"
 
 namespace sa {
-namespace {
-
-// The seeded walk: banded_affine_free_tb_kernel (sa_banded_affine_free.hip) with band_geom_seeded, the
-// pair's diagonal read from behind the launch's idx entries.  A kernel of its own for that kernel's
-// reason: a template parameter more would rename the existing instances, and a shared body changed
-// their registers.
-template <bool LUT>
-__global__ __launch_bounds__(64) void banded_affine_seeded_tb_kernel(BandAffineParams P) {
-    const uint32_t q = blockIdx.x * 64 + threadIdx.x;
-    if (q >= P.count) return;
-    const uint32_t pair = P.idx[q];
-    const uint64_t a1 = P.off1[pair], a2 = P.off2[pair];
-    const int32_t m = (int32_t)(P.off1[pair + 1] - a1), n = (int32_t)(P.off2[pair + 1] - a2);
-    const uint8_t* s1 = P.seq1 + a1;
-    const uint8_t* s2 = P.seq2 + a2;
-    const BandGeom bg = band_geom_seeded(m, n, (int32_t)P.band, (int32_t)P.idx[P.count + q]);
-    const uint32_t* rec = P.rec + P.recoff[q];
-    sa_result* res = P.res + pair;
-    uint8_t* ops = P.ops + a1 + a2 + pair;
-    const int R = P.R, L = P.L, S = R <= 8 ? 8 / R : 1, WPS = R <= 8 ? 1 : R / 8;
-    const bool stop_i0 = (P.free_ends & kFreeSeq2Begin) != 0, stop_j0 = (P.free_ends & kFreeSeq1Begin) != 0;
-    int32_t i = res->end_i, j = res->end_j;
-    if (i < 0 || i > m || j < 0 || j > n) i = j = 0;   // (never: the fill's end cell is a cell)
-    uint32_t nops = 0;
-    const uint32_t cap = (uint32_t)(m + n);            // (never reached: every op consumes a symbol)
-    int type = 0;
-    while ((i > 0 || j > 0) && nops < cap) {
-        if ((i == 0 && stop_i0) || (j == 0 && stop_j0)) break;
-        if (i == 0) { ops[nops++] = 'L'; --j; continue; }
-        if (j == 0) { ops[nops++] = 'U'; --i; continue; }
-        const int32_t tp = i + j - bg.lo - bg.tb, c = j - i - bg.lo;
-        if (c < 0 || c >= bg.beff) break;   // (never: the walk stays inside the band)
-        const int32_t l = c / (2 * R), rr = (c % (2 * R)) >> 1;
-        uint32_t w;
-        if (R <= 8) w = rec[(uint64_t)(tp / S) * L + l] >> (((tp % S) * R + rr) * 4);
-        else w = rec[((uint64_t)tp * WPS + (rr >> 3)) * L + l] >> ((rr & 7) * 4);
-        if (type == 0) {
-            const uint32_t code = w & 3u;
-            if (code == 0) break;   // (never: a global cell's M has a source)
-            if (code == 1) {
-                const uint32_t a = s1[i - 1], b = s2[j - 1];
-                const bool v = LUT ? ((P.lutbits[(a << 3) | (b >> 5)] >> (b & 31)) & 1u) != 0 : a == b;
-                ops[nops++] = (v || P.allow) ? (v ? 'M' : 'S') : 'X';
-                --i;
-                --j;
-                continue;
-            }
-            type = (int)code - 1;
-        }
-        if (type == 1) {
-            ops[nops++] = 'U';
-            --i;
-            if (!(w & 4u)) type = 0;
-        } else {
-            ops[nops++] = 'L';
-            --j;
-            if (!(w & 8u)) type = 0;
-        }
-    }
-    res->start_i = i;
-    res->start_j = j;
-    res->nops = nops;
-    res->flags = 0;
-    res->reserved = 0;
-}
-
-}  // namespace
-
 hipError_t launch_banded_affine_seeded_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
-    constexpr int kMode = kMatchFreeBit | kMatchSeedBit;
-    return lut ? launch_band_affine_fill_alg<false, kMatchLut | kMode>(variant, rec, p, s)
-               : launch_band_affine_fill_alg<false, kMatchEq | kMode>(variant, rec, p, s);
+    return lut ? launch_band_sweep<BandAffineFill, SA_GLOBAL_GOTOH, kBandSeeded, kMatchLut>(variant, rec, p, s)
+               : launch_band_sweep<BandAffineFill, SA_GLOBAL_GOTOH, kBandSeeded, kMatchEq>(variant, rec, p, s);
 }
 
 hipError_t launch_banded_affine_seeded_tb(bool lut, const BandAffineParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
-    const dim3 grid((p.count + 63) / 64), block(64);
-    if (lut) hipLaunchKernelGGL((banded_affine_seeded_tb_kernel<true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((banded_affine_seeded_tb_kernel<false>), grid, block, 0, s, p);
-    return hipGetLastError();
+    return launch_band_affine_tb<kBandSeeded>(SA_GLOBAL_GOTOH, lut, p, s);
 }
 }  // namespace sa

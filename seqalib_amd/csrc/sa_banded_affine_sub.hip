@@ -7,7 +7,7 @@ namespace sa {
 hipError_t launch_banded_affine_fill_sub(int algo, int variant, bool rec, const BandAffineParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
     if (!p.submat || p.sub_k < 1 || p.sub_k > (uint32_t)kSubMaxSyms) return hipErrorInvalidValue;
-    return algo == SA_LOCAL_GOTOH ? launch_band_affine_fill_alg<true, kMatchSub>(variant, rec, p, s)
-                                  : launch_band_affine_fill_alg<false, kMatchSub>(variant, rec, p, s);
+    return algo == SA_LOCAL_GOTOH ? launch_band_sweep<BandAffineFill, SA_LOCAL_GOTOH, kBandCorridor, kMatchSub>(variant, rec, p, s)
+                                  : launch_band_sweep<BandAffineFill, SA_GLOBAL_GOTOH, kBandCorridor, kMatchSub>(variant, rec, p, s);
 }
 }  // namespace sa

@@ -1,4 +1,4 @@
-// Device-planned seeded (kBandAlgSeededDev) instantiations of the banded NW fill and walk
+// Device-planned seeded (kBandSeededDev) instantiations of the banded NW fill and walk
 // (sa_align_batch_banded_seeded_device, sa_score_batch_banded_seeded_device with SA_NW / SA_HIRSCHBERG): the
 // seeded mode with the lists' lengths and every pair's description read from device memory, where the planner
 // (sa_band_planner.hip) left them.  kMatchEq and kMatchLut, recording and record-free, every variant.  A
@@ -10,16 +10,13 @@ namespace sa {
 // variant's list return at once.
 hipError_t launch_banded_seeded_dev_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
-    return lut ? launch_band_fill_alg<kBandAlgSeededDev, kMatchLut>(variant, rec, p, s)
-               : launch_band_fill_alg<kBandAlgSeededDev, kMatchEq>(variant, rec, p, s);
+    return lut ? launch_band_sweep<BandFill, SA_NW, kBandSeededDev, kMatchLut>(variant, rec, p, s)
+               : launch_band_sweep<BandFill, SA_NW, kBandSeededDev, kMatchEq>(variant, rec, p, s);
 }
 
 // One launch over the chunk's plan records: a lane per pair, R and L from the pair's variant.
 hipError_t launch_banded_seeded_dev_tb(bool lut, const BandParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
-    const dim3 grid((p.count + 63) / 64), block(64);
-    if (lut) hipLaunchKernelGGL((banded_tb_kernel<kBandAlgSeededDev, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((banded_tb_kernel<kBandAlgSeededDev, false>), grid, block, 0, s, p);
-    return hipGetLastError();
+    return launch_band_tb<kBandSeededDev>(SA_NW, lut, p, s);
 }
 }  // namespace sa

@@ -6,7 +6,7 @@ namespace sa {
 hipError_t launch_banded_fill_sub(int algo, int variant, bool rec, const BandParams& p, hipStream_t s) {
     if (!p.count) return hipSuccess;
     if (!p.submat || p.sub_k < 1 || p.sub_k > (uint32_t)kSubMaxSyms) return hipErrorInvalidValue;
-    return algo == SA_SW ? launch_band_fill_alg<SA_SW, kMatchSub>(variant, rec, p, s)
-                         : launch_band_fill_alg<SA_NW, kMatchSub>(variant, rec, p, s);
+    return algo == SA_SW ? launch_band_sweep<BandFill, SA_SW, kBandCorridor, kMatchSub>(variant, rec, p, s)
+                         : launch_band_sweep<BandFill, SA_NW, kBandCorridor, kMatchSub>(variant, rec, p, s);
 }
 }  // namespace sa

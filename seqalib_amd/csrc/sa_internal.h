@@ -477,16 +477,36 @@ static_assert(sizeof(BandParams) == 128, "free_ends fills the tail padding");
 hipError_t launch_banded_fill(int algo, int variant, int mm, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_fill_sub(int algo, int variant, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_tb(int algo, bool lut, const BandParams& p, hipStream_t s);
-// The ends-free NW band (sa_banded_free.hip): the fill template's internal algorithm value (no public
-// algo: the calls take SA_NW / SA_HIRSCHBERG), its kMatchEq / kMatchLut fills and its walk.
-constexpr int kBandAlgFree = 100;
+// The band modes: where a pair's band lies, which cells may begin and end its alignment, and where the
+// launch is described.  Both fills and both walks take one as a template parameter; the algorithm parameter
+// beside it is the algorithm (SA_SW / SA_NW, local / global) and the match mode the match mode.  Every mode
+// but the corridor is the global algorithm's (NW, GlobalGotoh).
+enum BandMode {
+    kBandCorridor,    // band_geom round (0, 0) .. (m, n); sa_banded.hip, sa_banded_affine.hip and the _sub units
+    kBandFree,        // the corridor with free ends (BandParams::free_ends); sa_banded[_affine]_free.hip
+    kBandSeeded,      // ends-free round a seed diagonal (band_geom_seeded); sa_banded[_affine]_seeded.hip
+    kBandExtend,      // anchored at (0, 0), free to end at any interior cell, X-drop; sa_banded_extend.hip (the affine
+                      // unit stands on its own code: sa_banded_affine_extend.hip says why)
+    kBandSeededDev    // kBandSeeded with the launch described in device memory; sa_banded[_affine]_seeded_dev.hip
+};
+constexpr bool band_mode_free(BandMode mode) { return mode == kBandFree || mode == kBandSeeded || mode == kBandSeededDev; }
+constexpr bool band_mode_ext(BandMode mode) { return mode == kBandExtend; }
+constexpr bool band_mode_planned(BandMode mode) { return mode == kBandSeededDev; }
+// idx[count + q] holds the seed diagonal of the pair idx[q] (BandParams is full); the planned mode's is in its plan record
+constexpr bool band_mode_diag_behind_idx(BandMode mode) { return mode == kBandSeeded; }
+// A pair's band in a mode; diag is read by the seeded modes only.
+template <BandMode MODE>
+__host__ __device__ inline BandGeom band_mode_geom(int32_t m, int32_t n, int32_t w, int32_t diag) {
+    return MODE == kBandCorridor || MODE == kBandFree ? band_geom(m, n, w) : band_geom_seeded(m, n, w, MODE == kBandExtend ? 0 : diag);
+}
 constexpr uint32_t kFreeSeq1Begin = 1, kFreeSeq1End = 2, kFreeSeq2Begin = 4, kFreeSeq2End = 8;   // SA_FREE_*
+// The ends-free NW band (sa_banded_free.hip; no public algo: the calls take SA_NW / SA_HIRSCHBERG): its
+// kMatchEq / kMatchLut fills and its walk.
 hipError_t launch_banded_free_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_free_tb(bool lut, const BandParams& p, hipStream_t s);
-// The seeded ends-free NW band (sa_banded_seeded.hip; sa_align_batch_banded_seeded): kBandAlgFree's fill
+// The seeded ends-free NW band (sa_banded_seeded.hip; sa_align_batch_banded_seeded): kBandFree's fill
 // and walk with band_geom_seeded.  BandParams is full, so the seed diagonals travel behind the launch's
 // idx entries: idx[count + q] is the diagonal (an int32) of the pair idx[q].  Only these kernels read it.
-constexpr int kBandAlgSeeded = 101;
 hipError_t launch_banded_seeded_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_seeded_tb(bool lut, const BandParams& p, hipStream_t s);
 // The device-planned seeded band (sa_banded_seeded_dev.hip, sa_banded_affine_seeded_dev.hip;
@@ -495,13 +515,11 @@ hipError_t launch_banded_seeded_tb(bool lut, const BandParams& p, hipStream_t s)
 // off1 = the chunk's plan records, off2 = the {first entry, length} words of the variant's list (fills),
 // idx = the chunk's lists, count = the pairs of the chunk -- the fill grid covers that many in every variant,
 // the walk's one launch that many plan records; recoff, seq1, seq2, R and L are not read.
-constexpr int kBandAlgSeededDev = 103;
 hipError_t launch_banded_seeded_dev_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_seeded_dev_tb(bool lut, const BandParams& p, hipStream_t s);
 // The NW extension band (sa_banded_extend.hip; sa_align_batch_banded_extend): NW's cell in the band
 // band_geom_seeded(m, n, w, 0), SW's running maximum from (0, 0) on, and the X-drop test.  The call's
 // xdrop (an int32, SA_XDROP_OFF included) travels in BandParams::free_ends; no diagonals follow idx.
-constexpr int kBandAlgExtend = 102;
 hipError_t launch_banded_extend_fill(int variant, bool lut, bool rec, const BandParams& p, hipStream_t s);
 hipError_t launch_banded_extend_tb(bool lut, const BandParams& p, hipStream_t s);
 
@@ -534,10 +552,10 @@ hipError_t launch_banded_affine_free_tb(bool lut, const BandAffineParams& p, hip
 // behind idx, as above.
 hipError_t launch_banded_affine_seeded_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_seeded_tb(bool lut, const BandAffineParams& p, hipStream_t s);
-// The device-planned seeded GlobalGotoh band (sa_banded_affine_seeded_dev.hip): as kBandAlgSeededDev above.
+// The device-planned seeded GlobalGotoh band (sa_banded_affine_seeded_dev.hip): as kBandSeededDev above.
 hipError_t launch_banded_affine_seeded_dev_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_seeded_dev_tb(bool lut, const BandAffineParams& p, hipStream_t s);
-// The GlobalGotoh extension band (sa_banded_affine_extend.hip): as kBandAlgExtend above.
+// The GlobalGotoh extension band (sa_banded_affine_extend.hip): as kBandExtend above.
 hipError_t launch_banded_affine_extend_fill(int variant, bool lut, bool rec, const BandAffineParams& p, hipStream_t s);
 hipError_t launch_banded_affine_extend_tb(bool lut, const BandAffineParams& p, hipStream_t s);
 }  // namespace sa

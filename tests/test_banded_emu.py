@@ -83,7 +83,7 @@ def emu(tmp_path_factory):
     out = keep or str(tmp_path_factory.mktemp("banded_emu"))
     os.makedirs(out, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in ("sa_internal.h", "sa_layout.h", "sa_band_plan.h", "sa_band_group.h",
-                                                "sa_banded_fill.h", "sa_banded_affine_fill.h")]
+                                                "sa_band_sweep.h", "sa_banded_fill.h", "sa_banded_affine_fill.h")]
     headers += [os.path.join(SHIM, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "seqalib_hip.h")]
     t0 = time.time()
 

@@ -19,22 +19,20 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-devic
          "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
 NAME = re.compile(r"Function Name: _ZN2sa11fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
 FIELD = re.compile(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
-BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_118banded_fill_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d)ELb(\d)E")
-AFFINE = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb(\d)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
+# the banded fills: band_sweep_kernel<BandFill | BandAffineFill<algorithm, BandMode, R, L, match mode, REC>>
+BANDED = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_117band_sweep_kernelINS\d+_(?:8BandFill|14BandAffineFill)"
+                    r"ILi(\d+)ELNS_8BandModeE(\d)ELi(\d+)ELi(\d+)ELi(\d)ELb(\d)E")
+# sa_banded_affine_extend.hip alone keeps the fills it had before the shared sweep (its header says why):
+# banded_affine_fill_kernel<LOCAL, R, L, match mode | kMatchExtBit, REC>
+AFFINE_EXT = re.compile(r"Function Name: _ZN2sa\d+_GLOBAL__N_125banded_affine_fill_kernelILb0ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
+MATCH_EXT_BIT = 32
 SO2 = re.compile(r"Function Name: _ZN2sa15fill_so2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E")
 CELL = ["i16 6-op", "f16 5-op", "f16 4-op"]
 ALG = ["SW", "NW", "LocalGotoh", "GlobalGotoh"]
-# the ends-free banded fills (sa_banded_free.hip, sa_banded_affine_free.hip): the linear fill's internal
-# algorithm value kBandAlgFree, and kMatchFreeBit in the affine fill's match-mode value
-# the seeded fills (sa_banded_seeded.hip, sa_banded_affine_seeded.hip): kBandAlgSeeded, and kMatchSeedBit beside
-# kMatchFreeBit
-BAND_ALG_FREE, MATCH_FREE_BIT = 100, 8
-BAND_ALG_SEEDED, MATCH_SEED_BIT = 101, 16
-# the extension fills (sa_banded_extend.hip, sa_banded_affine_extend.hip): kBandAlgExtend, and kMatchExtBit alone
-BAND_ALG_EXTEND, MATCH_EXT_BIT = 102, 32
-FREE = {1: "NW free", 3: "GGotoh free"}
-SEEDED = {1: "NW seeded", 3: "GGotoh seeded"}
-EXTEND = {1: "NW extend", 3: "GGotoh extend"}
+# BandMode (sa_internal.h): 0 the corridor, then the ends-free, seeded, extension and device-planned seeded
+# fills (sa_banded[_affine]_{free,seeded,extend,seeded_dev}.hip), which are NW's and GlobalGotoh's
+MODE = [None, {1: "NW free", 3: "GGotoh free"}, {1: "NW seeded", 3: "GGotoh seeded"}, {1: "NW extend", 3: "GGotoh extend"},
+        {1: "NW planned", 3: "GGotoh planned"}]
 MM = ["eq", "lut", "bits", "sub"]
 
 
@@ -54,16 +52,14 @@ def parse(text):
             rows.append(cur)
             continue
         m = BANDED.search(line)
-        if m:   # the banded fills (sa_banded.hip): algorithm, R, L, match mode, REC
-            g = tuple(int(x) for x in m.groups())
-            cur = {"banded": ((1, 1) if g[0] == BAND_ALG_FREE else (1, 2) if g[0] == BAND_ALG_SEEDED else (1, 3) if g[0] == BAND_ALG_EXTEND else (g[0], 0)) + g[1:]}
+        if m:   # the banded fills: algorithm (SA_SW .. SA_GLOBAL_GOTOH), mode, R, L, match mode, REC
+            cur = {"banded": tuple(int(x) for x in m.groups())}
             rows.append(cur)
             continue
-        m = AFFINE.search(line)
-        if m:   # the banded affine fills (sa_banded_affine.hip): LOCAL, R, L, match mode, REC
+        m = AFFINE_EXT.search(line)
+        if m:   # GlobalGotoh (3), extension (mode 3), R, L, match mode, REC
             g = tuple(int(x) for x in m.groups())
-            mode = 3 if g[3] & MATCH_EXT_BIT else 2 if g[3] & MATCH_SEED_BIT else int(bool(g[3] & MATCH_FREE_BIT))
-            cur = {"banded": (3 - g[0], mode) + g[1:3] + (g[3] & ~(MATCH_FREE_BIT | MATCH_SEED_BIT | MATCH_EXT_BIT), g[4])}
+            cur = {"banded": (3, 3, g[0], g[1], g[2] & ~MATCH_EXT_BIT, g[3])}
             rows.append(cur)
             continue
         m = SO2.search(line)
@@ -104,8 +100,8 @@ def main(argv):
         print(f"{'banded':<{wide}}{'R':>3}{'L':>4} {'match':<5}{'records':>8}{'VGPRs':>6}{'AGPRs':>6}{'SGPRs':>6}{'scratch':>8}{'waves':>6}{'LDS':>7}")
         bad_banded = 0
         for r in banded:
-            alg, free, R, L, lut, rec = r["banded"]
-            print(f"{EXTEND[alg] if free == 3 else SEEDED[alg] if free == 2 else FREE[alg] if free else ALG[alg]:<{wide}}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
+            alg, mode, R, L, lut, rec = r["banded"]
+            print(f"{MODE[mode][alg] if mode else ALG[alg]:<{wide}}{R:>3}{L:>4} {MM[lut]:<5}{rec:>8}{r['VGPRs']:>6}{r.get('AGPRs', 0):>6}{r['TotalSGPRs']:>6}{r['ScratchSize']:>8}"
                   f"{r['Occupancy']:>6}{r['LDS']:>7}")
             bad_banded += r["ScratchSize"] != 0
         print(f"# {len(banded)} banded kernels, {bad_banded} with scratch")
